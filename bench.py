@@ -1,6 +1,7 @@
 """bench.py -- superphotons/s of the MI355X transport engine on the dump019-class config.
 
     python bench.py [--gpus N] [--steps K] [--warmup W] [--photon-n 1e6] [--grid 192] [--scaling weak|strong]
+                    [--dump-outputs DIR] [--full]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 \\
         --master-port P bench.py --gpus N --steps K --warmup W
 
@@ -18,9 +19,26 @@ run.  value = superphotons created by all ranks in the K passes / max-over-ranks
 passes -- the reference's "Final rate" (created / elapsed of run_simulation, harm_model.cpp:407-409)
 averaged over K runs.
 
-detail.overlapped (1 GPU only, --overlap J, default 16): J such passes in flight at once (J engines,
-own streams and buffers, distinct seeds) -- device throughput when independent runs share the GPU;
-it is NOT value.
+A plain run does only what value needs: set-up, the W warm-up passes, the K timed passes, the result
+line.  The roofline block comes with it: it is formed from the timed passes' own launch times and
+from committed counts, and runs nothing.  --full adds the legs that take runs of their own:
+cpu_baseline (--cpu-seconds), detail.overlapped (--overlap) and detail.cold_run; without --full these
+three are null.
+
+--dump-outputs DIR: after the timed passes, what the last of them (seed 123 + K - 1) returned to its
+caller is written to DIR: spectrum.npy, float64 [6 theta bins, 200 energy bins, 13 fields in
+grmonty_amd.SPEC_FIELDS order] (with several ranks the job's reduced spectrum, written by rank 0), and
+counters.npy, float64 [superphotons created, recorded, scattered, max tau_scatt].  The dump and the
+seeds are fixed, so two builds given the same arguments run the same inputs: the superphotons created
+are the same number in every run.  The rest is a Monte Carlo estimate under the live adaptive bias,
+whose counters depend on the order in which the GPU retires photons, so it repeats
+only statistically: two runs of one build gave 17.64 M / 18.76 M recorded and 25.35 M / 27.65 M scattered
+for the pass of seed 132, and sparsely hit spectrum cells differ by far more.  Compare spectra
+summed over cells, or counters, with a tolerance of that size.
+
+detail.overlapped (--full, 1 GPU only, --overlap J, default 16): J such passes in flight at once (J
+engines, own streams and buffers, distinct seeds) -- device throughput when independent runs share
+the GPU; it is NOT value.
 
 Multi-GPU: one process per GPU.  --scaling weak (default): the job is photon_n x N, zone-sharded
 over the N ranks, rank r taking every N-th zone from zone r (grmonty_amd.zone_shards "strided": each
@@ -49,6 +67,7 @@ import argparse
 import json
 import os
 import sys
+import tempfile
 import time
 
 import numpy as np
@@ -56,7 +75,7 @@ import numpy as np
 REPO = os.path.dirname(os.path.abspath(__file__))
 sys.path.insert(0, os.path.join(REPO, "cuda-grmonty_amd"))
 import grmonty_amd as G  # noqa: E402  (load the engine's HIP runtime before anything else)
-from grmonty_amd.synth_dump import ensure_dump  # noqa: E402
+from grmonty_amd.synth_dump import write_dump  # noqa: E402
 
 ALG_BYTES_PER_STEP = 304  # per transport step: HARM gather 8x4x8 + hotcross 4x8 + K2 2x8
 HBM_PEAK_GBS = 8000.0     # MI355X_MICROARCH.md chip table (spec)
@@ -80,14 +99,24 @@ def parse():
                          "rank of BASELINE configs[3] -- photon_n 1e8 over 8 GPUs -- without the other ranks)")
     ap.add_argument("--grid", type=int, default=192)
     ap.add_argument("--dump", default="", help="HARM dump to use (default: synthetic dump019-class)")
-    ap.add_argument("--cpu-seconds", type=float, default=15.0, help="bounded CPU-baseline sample (0 = skip)")
+    ap.add_argument("--full", action="store_true",
+                    help="also run the legs beside the headline figure: the CPU baseline (--cpu-seconds), the "
+                         "overlapped-throughput figure (--overlap) and the cold run")
+    ap.add_argument("--dump-outputs", default="", metavar="DIR",
+                    help="write the results of the last timed pass to DIR/spectrum.npy and DIR/counters.npy")
+    ap.add_argument("--cpu-seconds", type=float, default=15.0,
+                    help="--full: bounded CPU-baseline sample (0 = skip)")
     ap.add_argument("--threads", type=int, default=0)
     ap.add_argument("--overlap", type=int, default=16,
-                    help="detail only: passes in flight for the overlapped-throughput figure (0 = skip; 1 GPU)")
+                    help="--full, detail only: passes in flight for the overlapped-throughput figure "
+                         "(0 = skip; 1 GPU)")
     ap.add_argument("--pmc-summary", default=os.environ.get("GRM_PMC_SUMMARY", ""),
                     help="rocprofv3 --pmc counter CSVs, comma-separated (FETCH_SIZE pass, WRITE_SIZE pass) "
                          "of this same command, to fill roofline.traffic")
-    return ap.parse_args()
+    args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be at least 1 and --warmup at least 0")
+    return args
 
 
 def host_threads(world: int) -> int:
@@ -195,7 +224,7 @@ def main():
     world = int(os.environ.get("WORLD_SIZE", "1"))
     rank = int(os.environ.get("RANK", "0"))
     local = int(os.environ.get("LOCAL_RANK", "0"))
-    overlap = args.overlap if world == 1 else 0
+    overlap = args.overlap if (world == 1 and args.full) else 0
     if overlap > 1:
         # one hardware queue per engine of the overlapped figure (+1); HIP reads it at runtime start
         os.environ["GPU_MAX_HW_QUEUES"] = str(min(32, max(4, overlap + 1)))
@@ -225,10 +254,12 @@ def main():
         part_rank, part_world = (int(v) for v in args.shard_of.split("/"))
         assert 0 <= part_rank < part_world
     photon_n_job = int(args.photon_n) * (part_world if args.scaling == "weak" else 1)
-    path = args.dump or os.path.join(REPO, "gpurun_out" if os.path.isdir(os.path.join(REPO, "gpurun_out")) else ".",
-                                     f"synth{args.grid}_r{rank}.dump")
-    if not args.dump:
-        ensure_dump(path, args.grid, args.grid)
+    # the synthetic dump goes to a temporary directory of this process (removed when it exits): the
+    # benchmark then also runs from a tree it may not write to, and leaves nothing behind in it
+    path = args.dump
+    if not path:
+        dump_dir = tempfile.TemporaryDirectory(prefix="grmonty_bench_")
+        path = write_dump(os.path.join(dump_dir.name, f"synth{args.grid}_r{rank}.dump"), args.grid, args.grid)
     t = time.time()
     model = G.Model.load(path, photon_n=photon_n_job).init(threads, device=local)
     t_init = time.time() - t
@@ -338,7 +369,7 @@ def main():
         spec, n_rec, n_scatt, max_tau = eng.finish()
         if st["n_dropped"] or st["n_abandoned"]:
             raise RuntimeError(f"pass seed {seed}: {st['n_dropped']} children dropped, {st['n_abandoned']} abandoned")
-        return n_dev, st, n_rec, n_scatt
+        return n_dev, st, n_rec, n_scatt, spec, max_tau
 
     def reduce_job(eng, first, n):
         """the job's one exchange: a grouped RCCL all-reduce of every pass's stashed results, then
@@ -374,7 +405,7 @@ def main():
         dist.barrier()
     elapsed = time.time() - t0
     if job is not None:  # the job-level results: the reduced counters of every pass
-        res = [(r[0], r[1], j[1], j[2]) for r, j in zip(res, job)]
+        res = [(r[0], r[1], j[1], j[2], j[0], j[3]) for r, j in zip(res, job)]
     n_rank = sum(r[0] for r in res)
     tmax, total = elapsed, n_rank
     if dist is not None:
@@ -383,28 +414,18 @@ def main():
         dist.all_reduce(tm, op=dist.ReduceOp.MAX)
         dist.all_reduce(tt, op=dist.ReduceOp.SUM)
         tmax, total = float(tm[0]), int(tt[0])
+    if args.dump_outputs:
+        created = [res[-1][0]]  # the last pass's superphotons: every rank's shard
+        if dist is not None:
+            created = [None] * world
+            dist.all_gather_object(created, res[-1][0])
+        if rank == 0:
+            dump_outputs(args.dump_outputs, res[-1][4], sum(created), res[-1][2], res[-1][3], res[-1][5])
 
     # cold run (detail, outside the timed region): the reference's own window alloc_memory ...
     # free_memory (harm_model.cpp:341-409) -- a fresh engine (device buffers, stream, events), the
     # zone table built on the host and uploaded, one pass of seed 123, destroy; every rank, one pass
-    cold = None
-    tc = time.time()
-    eng_c = G.Engine(model, device=local)
-    t_create = time.time() - tc
-    eng_c.emit_setup(model)
-    t_setup = time.time() - tc - t_create
-    tp = time.time()
-    n_c = one_pass(eng_c, SEED0, id_base[SEED0], None)[0] if SEED0 in id_base else None
-    t_pass = time.time() - tp
-    eng_c.close()
-    t_cold = time.time() - tc
-    cold = {"wall_s": t_cold, "engine_create_s": t_create, "emit_setup_s": t_setup, "pass_s": t_pass,
-            "destroy_s": t_cold - t_create - t_setup - t_pass, "superphotons": n_c,
-            "superphotons_per_s": (n_c / t_cold) if n_c else None,
-            "amortised_setup_s": t_create + t_setup,
-            "note": "one run_simulation pass in the reference's timing window alloc_memory..free_memory "
-                    "(harm_model.cpp:341-409): engine creation + zone-table upload + pass + destroy, rank 0; "
-                    "value amortises creation and setup over the job's passes"}
+    cold = cold_run(model, local, one_pass, id_base) if args.full else None
 
     overlapped = None
     if rank == 0 and overlap > 1:
@@ -430,7 +451,7 @@ def main():
         achieved_tf = big_steps * flops_step / (big_ms * 1e-3) / 1e12 if flops_step else None
         alg_gbs = big_steps * ALG_BYTES_PER_STEP / (big_ms * 1e-3) / 1e9
         cpu = None
-        if world == 1 and args.cpu_seconds > 0:
+        if world == 1 and args.full and args.cpu_seconds > 0:
             try:
                 ph = model.emit(seed=SEED0, z0=z0, z1=z1, threads=threads, stride=zst)
                 cpu = cpu_baseline(path, photon_n_job, ph, args.cpu_seconds)
@@ -513,6 +534,36 @@ def main():
         print(json.dumps(out), flush=True)
     if dist is not None:
         dist.destroy_process_group()
+
+
+def cold_run(model, local: int, one_pass, id_base: dict):
+    """detail only (--full): one pass of seed 123 on a fresh engine, timed from creation to destroy"""
+    tc = time.time()
+    eng_c = G.Engine(model, device=local)
+    t_create = time.time() - tc
+    eng_c.emit_setup(model)
+    t_setup = time.time() - tc - t_create
+    tp = time.time()
+    n_c = one_pass(eng_c, SEED0, id_base[SEED0], None)[0] if SEED0 in id_base else None
+    t_pass = time.time() - tp
+    eng_c.close()
+    t_cold = time.time() - tc
+    return {"wall_s": t_cold, "engine_create_s": t_create, "emit_setup_s": t_setup, "pass_s": t_pass,
+            "destroy_s": t_cold - t_create - t_setup - t_pass, "superphotons": n_c,
+            "superphotons_per_s": (n_c / t_cold) if n_c else None,
+            "amortised_setup_s": t_create + t_setup,
+            "note": "one run_simulation pass in the reference's timing window alloc_memory..free_memory "
+                    "(harm_model.cpp:341-409): engine creation + zone-table upload + pass + destroy, rank 0; "
+                    "value amortises creation and setup over the job's passes"}
+
+
+def dump_outputs(out_dir: str, spec: np.ndarray, created: int, n_rec: int, n_scatt: int, max_tau: float):
+    """--dump-outputs: the last timed pass's results as plain float64 arrays"""
+    os.makedirs(out_dir, exist_ok=True)
+    cells = np.stack([np.asarray(spec[f], dtype=np.float64) for f in G.SPEC_FIELDS], axis=-1)
+    np.save(os.path.join(out_dir, "spectrum.npy"), cells)
+    np.save(os.path.join(out_dir, "counters.npy"),
+            np.array([created, n_rec, n_scatt, max_tau], dtype=np.float64))
 
 
 def overlapped_throughput(model, jobs: int, z0: int, z1: int, zst: int = 1):

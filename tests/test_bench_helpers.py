@@ -46,6 +46,38 @@ def test_committed_traffic_has_provenance():
     assert same == (d.get("kernel_src_hash") == kernel_source_hash())
 
 
+def test_plain_run_is_the_default(monkeypatch):
+    """--full is off unless asked for, and a run needs at least one timed step"""
+    bench = pytest.importorskip("bench")
+    monkeypatch.setattr(sys, "argv", ["bench.py", "--gpus", "1", "--steps", "3", "--warmup", "2"])
+    a = bench.parse()
+    assert (a.steps, a.warmup, a.full, a.dump_outputs) == (3, 2, False, "")
+    monkeypatch.setattr(sys, "argv", ["bench.py", "--full", "--dump-outputs", "d"])
+    a = bench.parse()
+    assert a.full and a.dump_outputs == "d"
+    monkeypatch.setattr(sys, "argv", ["bench.py", "--steps", "0"])
+    with pytest.raises(SystemExit):
+        bench.parse()
+
+
+def test_dump_outputs_writes_plain_float64(tmp_path):
+    """--dump-outputs: the spectrum's 13 fields per cell in SPEC_FIELDS order and the four counters"""
+    import numpy as np
+    import grmonty_amd as G
+    bench = pytest.importorskip("bench")
+    spec = np.zeros((G.N_TH_BINS, G.N_E_BINS), dtype=G.SPECTRUM_CELL)
+    for k, f in enumerate(G.SPEC_FIELDS):
+        spec[f] = k + np.arange(G.N_TH_BINS * G.N_E_BINS).reshape(spec.shape) * 0.5
+    out = tmp_path / "o"
+    bench.dump_outputs(str(out), spec, 14506496, 17926711, 16832798, 2.5e-3)
+    s, c = np.load(out / "spectrum.npy"), np.load(out / "counters.npy")
+    assert s.dtype == np.float64 and s.shape == (G.N_TH_BINS, G.N_E_BINS, len(G.SPEC_FIELDS))
+    for k, f in enumerate(G.SPEC_FIELDS):
+        assert np.array_equal(s[..., k], spec[f])
+    assert c.dtype == np.float64 and c.tolist() == [14506496.0, 17926711.0, 16832798.0, 2.5e-3]
+    assert sorted(os.listdir(out)) == ["counters.npy", "spectrum.npy"]
+
+
 def test_borrowed_traffic_gives_no_hbm_rate(tmp_path, monkeypatch):
     """a traffic file measured on other kernel sources is reported as borrowed: committed_traffic
     says so, and bench.py then forms no measured HBM rate from it"""

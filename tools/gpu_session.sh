@@ -5,7 +5,7 @@
 #   tests  pytest -m gpu (TESTS = pytest selection, default the whole suite)
 #   smoke  __graft_entry__.smoke()
 #   pmc    PMC traffic passes (FETCH_SIZE, WRITE_SIZE: separate runs) of a short bench -> pmc_traffic.json
-#   bench  the default bench command (with that traffic when pmc ran)
+#   bench  the default bench command with --full (with that traffic when pmc ran)
 #   prof   rocprofv3 --kernel-trace --stats of the same passes run alone
 #   cfg3   BASELINE configs[3] rehearsal line: rank 0's shard of the 8-rank photon_n = 1e8 job
 #   mix    PMC instruction mix / VALU utilisation (diag pass, 192^2 photon_n=1e6)
@@ -35,6 +35,8 @@ python3 tools/traffic_summary.py "$F" "$W" "gpurun_out/${T}_pmc_FETCH_SIZE.log" 
 PS="--pmc-summary $F,$W"
 fi
 if has bench; then
+# --full: the session's bench line carries the CPU baseline, the overlapped figure and the cold run
+BENCH_ARGS="--full $BENCH_ARGS"
 timeout -k 10 900 python3 -u bench.py $PS $BENCH_ARGS > gpurun_out/${T}_bench.json 2> gpurun_out/${T}_bench.err || { echo bench failed; tail -5 gpurun_out/${T}_bench.err; exit 1; }
 tail -c 600 gpurun_out/${T}_bench.json
 fi
