@@ -33,6 +33,7 @@
 #include <rccl/rccl.h>
 
 #include "grm_device.h"
+#include "grm_cellsums.h"
 #include "grm_emit.h"
 
 using namespace grm;
@@ -2773,6 +2774,11 @@ struct grm_engine {
     size_t batch_cap = 0;
     grm_trace *d_trace = nullptr;
     unsigned long long trace_cap = 0;
+    /* cell sums binned from the trace (grm_engine_cell_sums_*): records [0, trace_consumed) are in
+     * the accumulator, GRM_CELLSUMS_DOUBLES doubles and then the skipped-record word; allocated by
+     * the first accumulate */
+    unsigned long long trace_consumed = 0;
+    double *d_cellsums = nullptr;
     uint64_t seed = 123;
     int bias_mode = 0;
     uint64_t id_base = 0;
@@ -3331,6 +3337,16 @@ int run_transport(grm_engine *e, const grm_init_photon *d_batch, size_t n) {
     return 0;
 }
 
+/* records the trace has counted (more than trace_cap: the excess was lost) */
+int trace_count(grm_engine *e, unsigned long long &cnt) {
+    HIPCHK(e, hipMemcpyAsync(&cnt, e->d_small + (3) * SMALL_STRIDE, sizeof(cnt), hipMemcpyDeviceToHost, e->stream));
+    HIPCHK(e, hipStreamSynchronize(e->stream));
+    return 0;
+}
+
+/* the cell-sum accumulator and its skipped-record word behind it */
+constexpr size_t CELLSUMS_BYTES = GRM_CELLSUMS_DOUBLES * sizeof(double) + sizeof(unsigned long long);
+
 int reset_counters(grm_engine *e) {
     CtlOp op{};
     op.reset = 1;
@@ -3475,6 +3491,7 @@ void grm_engine_destroy(grm_engine *e) {
     if (e->pin) hipHostFree(e->pin);
     hipFree(e->d_batch);
     hipFree(e->d_trace);
+    hipFree(e->d_cellsums);
     hipFree(e->d_upload);
     hipFree(e->d_timing);
     hipFree(e->d_waves);
@@ -3512,6 +3529,8 @@ int grm_engine_set_option(grm_engine *e, int opt, int64_t v) {
     case GRM_OPT_SEED: e->seed = (uint64_t)v; return 0;
     case GRM_OPT_BIAS_MODE: e->bias_mode = v ? 1 : 0; return 0;
     case GRM_OPT_TRACE_CAP:
+        /* the records counted so far are those of the old buffer (or of none): never binned */
+        if (trace_count(e, e->trace_consumed)) return -1;
         if (e->d_trace) hipFree(e->d_trace);
         e->d_trace = nullptr;
         e->trace_cap = 0;
@@ -3609,6 +3628,8 @@ int grm_engine_reset(grm_engine *e) {
     e->stats.kernel_ms = ms;
     e->stats.n_launches = launches;
     e->history = 0;
+    e->trace_consumed = 0; /* reset_counters zeroes the trace count */
+    if (e->d_cellsums) HIPCHK(e, hipMemsetAsync(e->d_cellsums, 0, CELLSUMS_BYTES, e->stream));
     return reset_counters(e);
 }
 
@@ -3631,6 +3652,116 @@ int64_t grm_engine_trace(grm_engine *e, grm_trace *out, size_t cap) {
     const size_t k = std::min(avail, cap);
     if (k && out && hipMemcpy(out, e->d_trace, k * sizeof(grm_trace), hipMemcpyDeviceToHost) != hipSuccess) return -1;
     return (int64_t)cnt;
+}
+
+int grm_engine_cell_sums_accumulate(grm_engine *e, uint64_t *n_binned, double *ms) {
+    if (!e) return -1;
+    if (n_binned) *n_binned = 0;
+    if (ms) *ms = 0.0;
+    HIPCHK(e, hipSetDevice(e->device));
+    if (!e->trace_cap) {
+        e->err = "cell sums: the trace is off (GRM_OPT_TRACE_CAP)";
+        return -1;
+    }
+    unsigned long long cnt = 0;
+    if (trace_count(e, cnt)) return -1;
+    if (cnt > e->trace_cap) {
+        e->err = "cell sums: the trace counted " + std::to_string(cnt) + " records but holds " +
+                 std::to_string(e->trace_cap) + " (GRM_OPT_TRACE_CAP): records were lost, nothing binned";
+        return -1;
+    }
+    if (!e->d_cellsums) {
+        HIPCHK(e, hipMalloc(&e->d_cellsums, CELLSUMS_BYTES));
+        HIPCHK(e, hipMemsetAsync(e->d_cellsums, 0, CELLSUMS_BYTES, e->stream));
+    }
+    const unsigned long long c0 = std::min(e->trace_consumed, cnt);
+    double t = 0.0;
+    if (grm_cellsums_launch(e->d_trace + c0, (size_t)(cnt - c0), e->d_cellsums,
+                            reinterpret_cast<unsigned long long *>(e->d_cellsums + GRM_CELLSUMS_DOUBLES), e->stream,
+                            e->ev0, e->ev1, &t, e->err))
+        return -1;
+    e->trace_consumed = cnt;
+    if (n_binned) *n_binned = cnt - c0;
+    if (ms) *ms = t;
+    return 0;
+}
+
+int grm_engine_cell_sums_read(grm_engine *e, double *out, uint64_t *n_skipped) {
+    if (!e || !out) return -1;
+    HIPCHK(e, hipSetDevice(e->device));
+    unsigned long long sk = 0;
+    if (!e->d_cellsums) {
+        std::memset(out, 0, GRM_CELLSUMS_DOUBLES * sizeof(double));
+    } else {
+        HIPCHK(e, hipMemcpyAsync(out, e->d_cellsums, GRM_CELLSUMS_DOUBLES * sizeof(double), hipMemcpyDeviceToHost,
+                                 e->stream));
+        HIPCHK(e, hipMemcpyAsync(&sk, e->d_cellsums + GRM_CELLSUMS_DOUBLES, sizeof(sk), hipMemcpyDeviceToHost,
+                                 e->stream));
+        HIPCHK(e, hipStreamSynchronize(e->stream));
+    }
+    if (n_skipped) *n_skipped = sk;
+    return 0;
+}
+
+int grm_engine_cell_sums_reset(grm_engine *e) {
+    if (!e) return -1;
+    HIPCHK(e, hipSetDevice(e->device));
+    if (e->d_cellsums) {
+        HIPCHK(e, hipMemsetAsync(e->d_cellsums, 0, CELLSUMS_BYTES, e->stream));
+        HIPCHK(e, hipStreamSynchronize(e->stream));
+    }
+    return 0;
+}
+
+int grm_engine_trace_rewind(grm_engine *e) {
+    if (!e) return -1;
+    HIPCHK(e, hipSetDevice(e->device));
+    unsigned long long cnt = 0;
+    if (trace_count(e, cnt)) return -1;
+    if (e->trace_cap && cnt > e->trace_consumed) {
+        e->err = "trace rewind: " + std::to_string(cnt - e->trace_consumed) +
+                 " records are not consumed yet (grm_engine_cell_sums_accumulate); a rewind would drop them";
+        return -1;
+    }
+    CtlOp op{};
+    op.set = 1u << 3; /* the trace count */
+    op.val[3] = 0;
+    if (ctl(e, op, true)) return -1;
+    e->trace_consumed = 0;
+    return 0;
+}
+
+void *grm_engine_cell_sums_device_ptr(grm_engine *e) { return e ? (void *)e->d_cellsums : nullptr; }
+
+int grm_probe_cell_sums(grm_engine *e, const grm_trace *host_records, size_t n, double *out, uint64_t *n_skipped) {
+    if (!e || !out || (!host_records && n)) return -1;
+    HIPCHK(e, hipSetDevice(e->device));
+    grm_trace *d_rec = nullptr;
+    double *d_acc = nullptr;
+    unsigned long long sk = 0;
+    int rc = 0;
+    hipError_t st = hipMalloc(&d_acc, CELLSUMS_BYTES);
+    if (st == hipSuccess && n) st = hipMalloc(&d_rec, n * sizeof(grm_trace));
+    if (st == hipSuccess) st = hipMemsetAsync(d_acc, 0, CELLSUMS_BYTES, e->stream);
+    if (st == hipSuccess && n)
+        st = hipMemcpyAsync(d_rec, host_records, n * sizeof(grm_trace), hipMemcpyHostToDevice, e->stream);
+    if (st == hipSuccess)
+        rc = grm_cellsums_launch(d_rec, n, d_acc, reinterpret_cast<unsigned long long *>(d_acc + GRM_CELLSUMS_DOUBLES),
+                                 e->stream, e->ev0, e->ev1, nullptr, e->err);
+    if (st == hipSuccess && rc == 0)
+        st = hipMemcpyAsync(out, d_acc, GRM_CELLSUMS_DOUBLES * sizeof(double), hipMemcpyDeviceToHost, e->stream);
+    if (st == hipSuccess && rc == 0)
+        st = hipMemcpyAsync(&sk, d_acc + GRM_CELLSUMS_DOUBLES, sizeof(sk), hipMemcpyDeviceToHost, e->stream);
+    if (st == hipSuccess) st = hipStreamSynchronize(e->stream);
+    hipFree(d_rec);
+    hipFree(d_acc);
+    if (st != hipSuccess) {
+        e->err = std::string("grm_probe_cell_sums: ") + hipGetErrorString(st);
+        return -1;
+    }
+    if (rc) return -1;
+    if (n_skipped) *n_skipped = sk;
+    return 0;
 }
 
 int grm_engine_upload(grm_engine *e, const grm_init_photon *batch, size_t n, grm_init_photon **dev_out) {

@@ -60,6 +60,7 @@ OPT_JOB_START_WAIT_MS = 28
 OPT_EARLY_CHILDREN = 29
 OPT_SPLIT, OPT_SPLIT_THR, OPT_SPLIT_SPIN, OPT_SPLIT_GTHR, OPT_SPLIT_BATCH = 23, 24, 25, 26, 27
 N_TH_BINS, N_E_BINS = 6, 200
+N_ORDERS, N_CELL_SUMS = 4, 5  # scattering orders 0, 1, 2, >= 3; moments n, sum w, sum w^2, sum wE, sum (wE)^2
 
 
 class Header(C.Structure):
@@ -131,6 +132,13 @@ SIGNATURES = {
     "grm_engine_download": (C.c_int, [VP, VP, C.c_size_t, VP]),
     "grm_probe": (C.c_int, [VP, C.c_int, DP, C.c_int, DP, C.c_int, C.c_size_t]),
     "grm_engine_upload": (C.c_int, [VP, VP, C.c_size_t, C.POINTER(VP)]),
+    "grm_engine_cell_sums_accumulate": (C.c_int, [VP, C.POINTER(C.c_uint64), DP]),
+    "grm_engine_cell_sums_read": (C.c_int, [VP, DP, C.POINTER(C.c_uint64)]),
+    "grm_engine_cell_sums_reset": (C.c_int, [VP]),
+    "grm_engine_trace_rewind": (C.c_int, [VP]),
+    "grm_engine_cell_sums_device_ptr": (VP, [VP]),
+    "grm_probe_cell_sums": (C.c_int, [VP, VP, C.c_size_t, DP, C.POINTER(C.c_uint64)]),
+    "grm_write_spectrum_orders": (C.c_int, [VP, DP, C.c_char_p]),
     "grm_rccl_unique_id": (C.c_int, [C.POINTER(C.c_uint8)]),
     "grm_engine_comm_init": (C.c_int, [VP, C.POINTER(C.c_uint8), C.c_int, C.c_int]),
     "grm_engine_allreduce": (C.c_int, [VP]),
@@ -297,6 +305,16 @@ class Model:
         if self.L.grm_write_spectrum_stats(self.h, _ptr(s), path.encode()) != 0:
             raise IOError(self.L.grm_model_last_error().decode())
 
+    def write_spectrum_orders(self, sums: np.ndarray, path: str):
+        """The spectrum by scattering order from Engine.cell_sums(): 200 rows of log10(E) and, per
+        theta bin and order 0, 1, 2, >= 3, nuLnu, sigma_nuLnu (independent-superphoton estimate: the
+        parent-child correlation of scattered photons is ignored) and n -- 73 columns."""
+        a = np.ascontiguousarray(sums, dtype=np.float64)
+        if a.size != N_ORDERS * N_TH_BINS * N_E_BINS * N_CELL_SUMS:
+            raise ValueError(f"cell sums: expected [{N_ORDERS}][{N_TH_BINS * N_E_BINS}][{N_CELL_SUMS}], got {a.shape}")
+        if self.L.grm_write_spectrum_orders(self.h, a.ctypes.data_as(DP), path.encode()) != 0:
+            raise IOError(self.L.grm_model_last_error().decode())
+
 
 class Engine:
     """cuda_super_photon replacement: device buffers + persistent transport kernel on one GPU."""
@@ -380,6 +398,41 @@ class Engine:
         if n < 0:
             raise RuntimeError("trace not enabled")
         return out[:min(n, cap)]
+
+    def cell_sums_accumulate(self) -> tuple[int, float]:
+        """Bin the trace records not binned yet into the engine's cell-sum accumulator, on the
+        device; returns (records walked, kernel ms).  Raises with the trace off or overflowed."""
+        n, ms = C.c_uint64(), C.c_double()
+        self._check(self.L.grm_engine_cell_sums_accumulate(self.h, C.byref(n), C.byref(ms)))
+        return int(n.value), float(ms.value)
+
+    def cell_sums(self) -> tuple[np.ndarray, int]:
+        """(sums [N_ORDERS, N_TH_BINS * N_E_BINS, N_CELL_SUMS], n_skipped): per scattering order
+        min(n_scatt, 3) and cell ix2 * 200 + i_e the moments n, sum w, sum w^2, sum wE, sum (wE)^2 of
+        the recorded superphotons accumulated so far; sums.sum(axis=0) is the all-orders table."""
+        out = np.zeros((N_ORDERS, N_TH_BINS * N_E_BINS, N_CELL_SUMS))
+        sk = C.c_uint64()
+        self._check(self.L.grm_engine_cell_sums_read(self.h, out.ctypes.data_as(DP), C.byref(sk)))
+        return out, int(sk.value)
+
+    def cell_sums_reset(self):
+        self._check(self.L.grm_engine_cell_sums_reset(self.h))
+
+    def trace_rewind(self):
+        """Empty the trace buffer for the next track call; raises while records are not binned."""
+        self._check(self.L.grm_engine_trace_rewind(self.h))
+
+    def cell_sums_device_ptr(self) -> int:
+        return int(self.L.grm_engine_cell_sums_device_ptr(self.h) or 0)
+
+    def probe_cell_sums(self, records: np.ndarray) -> tuple[np.ndarray, int]:
+        """the cell-sum kernel on host trace records (scratch buffers; the engine's trace and
+        accumulator stay as they are): (sums, n_skipped) as cell_sums()"""
+        r = np.ascontiguousarray(records, dtype=TRACE)
+        out = np.zeros((N_ORDERS, N_TH_BINS * N_E_BINS, N_CELL_SUMS))
+        sk = C.c_uint64()
+        self._check(self.L.grm_probe_cell_sums(self.h, _ptr(r), len(r), out.ctypes.data_as(DP), C.byref(sk)))
+        return out, int(sk.value)
 
     def upload(self, photons: np.ndarray) -> int:
         """Copy photons into an engine-owned device buffer; returns its device address."""

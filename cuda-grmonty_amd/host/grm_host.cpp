@@ -1001,6 +1001,41 @@ int grm_write_spectrum_stats(const grm_model *m, const grm_spectrum_cell *spec, 
     return ok ? 0 : set_err(std::string("write failed: ") + path);
 }
 
+/* The spectrum by scattering order with its standard error, from the cell sums: grm_write_spectrum's
+ * nuLnu factor on sum wE and on sqrt(sum (wE)^2).  The error is the independent-superphoton
+ * estimate: a scattered child is correlated with its parent, which it ignores. */
+int grm_write_spectrum_orders(const grm_model *m, const double *sums, const char *path) {
+    if (!m || !sums || !path) return set_err("null argument");
+    const grm_header &h = m->hdr;
+    const double dx2 = (h.x_stop[2] - h.x_start[2]) / (2 * GRM_N_TH_BINS);
+    auto d_omega = [&](double a, double b) {
+        return 2.0 * kPi *
+               (-std::cos(kPi * b + 0.5 * (1.0 - h.h_slope) * std::sin(2 * kPi * b)) +
+                std::cos(kPi * a + 0.5 * (1.0 - h.h_slope) * std::sin(2 * kPi * a)));
+    };
+    FILE *fp = std::fopen(path, "w");
+    if (!fp) return set_err(std::string("Cannot open file ") + path);
+    std::fprintf(fp,
+                 "# log10(E/me c^2); per theta bin 0..%d and scattering order 0, 1, 2, >=3: nuLnu sigma_nuLnu n "
+                 "(sigma: independent superphotons; parent-child correlation ignored)\n",
+                 GRM_N_TH_BINS - 1);
+    const size_t cells = (size_t)GRM_N_TH_BINS * GRM_N_E_BINS;
+    for (int i = 0; i < GRM_N_E_BINS; ++i) {
+        std::fprintf(fp, "%.17g", (i * SPEC_D_L_E + K.spec_l_e_0) / kLn10);
+        for (int j = 0; j < GRM_N_TH_BINS; ++j) {
+            const double dom = 2.0 * d_omega(j * dx2, (j + 1) * dx2);
+            const double fac = (ME * CL * CL) * (4.0 * kPi / dom) * (1.0 / SPEC_D_L_E);
+            for (int o = 0; o < GRM_N_ORDERS; ++o) {
+                const double *c = sums + ((size_t)o * cells + (size_t)j * GRM_N_E_BINS + i) * GRM_N_CELL_SUMS;
+                std::fprintf(fp, " %.17g %.17g %.17g", fac * c[3] / L_SUN, fac * std::sqrt(c[4]) / L_SUN, c[0]);
+            }
+        }
+        std::fprintf(fp, "\n");
+    }
+    const bool ok = std::fclose(fp) == 0;
+    return ok ? 0 : set_err(std::string("write failed: ") + path);
+}
+
 int grm_engine_create_from_model(const grm_model *m, int device, grm_engine **out) {
     if (!m || !m->inited) return set_err("model not initialised");
     const double *f[8];

@@ -5,9 +5,14 @@
  *   grmonty_amd --harm_dump_path=DUMP --spectrum_path=OUT [--photon_n=5000000]
  *               [--mass_unit=4e19] [--verbosity=info] [--device=0] [--seed=123]
  *               [--batch=67108864] [--threads=0] [--host_emit] [--stats_path=OUT.stats]
+ *               [--orders_path=OUT.orders] [--trace_cap=N]
  *
  * read_file -> init -> run_simulation (zone batches emitted and tracked on the GPU; --host_emit:
  * emitted on host threads, batch b+1 overlapping the transport of batch b) -> report_spectrum.
+ * --orders_path: the spectrum by scattering order with standard errors (grm_write_spectrum_orders);
+ * the run then keeps the per-photon trace, bins it on the GPU after every zone batch
+ * (grm_engine_cell_sums_accumulate) and rewinds it.  --trace_cap: trace records per batch (default:
+ * TRACE_PER_PHOTON x the batch's emitted photons); a batch that needs more ends the run with an error.
  * "Final rate" = created superphotons / wall time of run_simulation, as in the reference.
  */
 #include <chrono>
@@ -52,16 +57,24 @@ bool flag(int argc, char **argv, int &i, const char *name, std::string &val) {
     return false;
 }
 
+/* Default trace capacity of a zone batch, in records per emitted photon: twice the largest
+ * tracked / primaries ratio measured -- 4.39 at 64^2, photon_n = 2000; 2.54 at 192^2, 1e5; 2.23 at
+ * 192^2, 1e6 (profiles/cell_sums_measure.json).  The ratio grows as photon_n
+ * shrinks (the adaptive bias scatters more per photon) and in the first batch of a job cut into
+ * many: such a run says how many records it needed and wants --trace_cap. */
+constexpr double TRACE_PER_PHOTON = 8.8;
+
 } /* namespace */
 
 int main(int argc, char **argv) {
     long long photon_n = 5000000; /* main.cpp:20 */
     double mass_unit = 4e19;      /* main.cpp:21 */
-    std::string dump, spec_path, stats_path, verbosity = "info";
+    std::string dump, spec_path, stats_path, orders_path, verbosity = "info";
     int device = 0, threads = 0;
     unsigned long long seed = 123; /* consts.hpp:14 */
     long long batch = 1ll << 26; /* photons per zone batch (8.6 GB of emitted photons) */
     bool host_emit = false;
+    long long trace_cap = 0; /* --trace_cap; 0 = TRACE_PER_PHOTON x the batch */
     for (int i = 1; i < argc; ++i) {
         std::string v;
         if (flag(argc, argv, i, "photon_n", v)) photon_n = std::atoll(v.c_str());
@@ -70,6 +83,8 @@ int main(int argc, char **argv) {
         else if (flag(argc, argv, i, "spectrum_path", v)) spec_path = v;
         else if (flag(argc, argv, i, "verbosity", v)) verbosity = v;
         else if (flag(argc, argv, i, "stats_path", v)) stats_path = v;
+        else if (flag(argc, argv, i, "orders_path", v)) orders_path = v;
+        else if (flag(argc, argv, i, "trace_cap", v)) trace_cap = std::atoll(v.c_str());
         else if (flag(argc, argv, i, "device", v)) device = std::atoi(v.c_str());
         else if (flag(argc, argv, i, "seed", v)) seed = std::strtoull(v.c_str(), nullptr, 10);
         else if (flag(argc, argv, i, "batch", v)) batch = std::atoll(v.c_str());
@@ -138,11 +153,32 @@ int main(int argc, char **argv) {
         buf.resize((size_t)std::max<int64_t>(n, 0));
         if (n > 0) grm_model_emit(m, seed, cuts[b], cuts[b + 1], buf.data(), buf.size(), threads);
     };
+    /* --orders_path: size the trace for the batch about to be tracked, and bin + rewind it after */
+    const bool orders = !orders_path.empty();
+    long long cap_now = 0;
+    auto trace_for = [&](size_t n) {
+        const long long want = trace_cap > 0 ? trace_cap : (long long)(TRACE_PER_PHOTON * (double)n) + 1024;
+        if (want <= cap_now) return 0;
+        cap_now = want;
+        return grm_engine_set_option(e, GRM_OPT_TRACE_CAP, want);
+    };
+    auto bin_trace = [&]() {
+        uint64_t nb = 0;
+        double ms = 0.0;
+        if (grm_engine_cell_sums_accumulate(e, &nb, &ms) || grm_engine_trace_rewind(e)) return -1;
+        info("Binned %llu trace records by scattering order in %.3f ms", (unsigned long long)nb, ms);
+        return 0;
+    };
     if (host_emit) emit(0, cur);
     for (size_t b = 0; b + 1 < cuts.size(); ++b) {
         if (host_emit) {
             std::thread prod;
             if (b + 2 < cuts.size()) prod = std::thread(emit, b + 1, std::ref(nxt));
+            if (orders && !cur.empty() && trace_for(cur.size())) {
+                std::fprintf(stderr, "[error] trace: %s\n", grm_engine_last_error(e));
+                if (prod.joinable()) prod.join();
+                return 1;
+            }
             if (!cur.empty() && grm_engine_track(e, cur.data(), cur.size())) {
                 std::fprintf(stderr, "[error] transport: %s\n", grm_engine_last_error(e));
                 if (prod.joinable()) prod.join();
@@ -155,12 +191,16 @@ int main(int argc, char **argv) {
         } else {
             grm_init_photon *d_ph = nullptr;
             uint64_t n = 0;
-            if (grm_engine_emit(e, seed, cuts[b], cuts[b + 1], &d_ph, &n) ||
+            if (grm_engine_emit(e, seed, cuts[b], cuts[b + 1], &d_ph, &n) || (orders && n && trace_for(n)) ||
                 (n && grm_engine_track_device(e, d_ph, n))) {
                 std::fprintf(stderr, "[error] emission/transport: %s\n", grm_engine_last_error(e));
                 return 1;
             }
             created += n;
+        }
+        if (orders && cap_now && bin_trace()) {
+            std::fprintf(stderr, "[error] cell sums: %s\n", grm_engine_last_error(e));
+            return 1;
         }
         const double el = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
         info("Rate %.2f ph/s, zone batch %zu/%zu", created / el, b + 1, cuts.size() - 1);
@@ -198,6 +238,21 @@ int main(int argc, char **argv) {
     if (!stats_path.empty() && grm_write_spectrum_stats(m, spec.data(), stats_path.c_str())) {
         std::fprintf(stderr, "[error] %s\n", grm_model_last_error());
         return 1;
+    }
+    if (orders) {
+        std::vector<double> sums((size_t)GRM_N_ORDERS * GRM_N_TH_BINS * GRM_N_E_BINS * GRM_N_CELL_SUMS);
+        uint64_t skipped = 0;
+        if (grm_engine_cell_sums_read(e, sums.data(), &skipped)) {
+            std::fprintf(stderr, "[error] cell sums: %s\n", grm_engine_last_error(e));
+            return 1;
+        }
+        if (skipped) std::fprintf(stderr, "[warn] cell sums: %llu recorded photons outside the grid skipped\n",
+                                  (unsigned long long)skipped);
+        info("Writing spectrum by scattering order to file %s", orders_path.c_str());
+        if (grm_write_spectrum_orders(m, sums.data(), orders_path.c_str())) {
+            std::fprintf(stderr, "[error] %s\n", grm_model_last_error());
+            return 1;
+        }
     }
     grm_engine_destroy(e);
     grm_model_free(m);

@@ -38,6 +38,10 @@ extern "C" {
 #define GRM_HC_N_W 220
 #define GRM_HC_N_T 80
 #define GRM_NINT 20000
+/* cell sums by scattering order (grm_engine_cell_sums_*): orders 0, 1, 2, >= 3; per cell the
+ * moments n, sum w, sum w^2, sum wE, sum (wE)^2 of the recorded superphotons */
+#define GRM_N_ORDERS 4
+#define GRM_N_CELL_SUMS 5
 
 /* harm_data.hpp:19-44 -- HARM dump header (same field order/types as the reference) */
 typedef struct grm_header {
@@ -239,6 +243,32 @@ int grm_engine_stats(const grm_engine *e, grm_stats *out);
 void *grm_engine_spectrum_device_ptr(grm_engine *e);
 /* copy the per-photon trace (requires GRM_OPT_TRACE_CAP > 0); returns records produced. */
 int64_t grm_engine_trace(grm_engine *e, grm_trace *out, size_t cap);
+/* --- cell sums by scattering order, binned on the device from the trace ------------------ */
+/* sums[GRM_N_ORDERS][GRM_N_TH_BINS * GRM_N_E_BINS][GRM_N_CELL_SUMS] doubles: per order
+ * min(n_scatt, 3) and cell ix2 * GRM_N_E_BINS + i_e the moments n, sum w, sum w^2, sum wE and
+ * sum (wE)^2 over the recorded superphotons (end_reason 0) of the trace -- what a standard error, a
+ * Kish effective N or a KS comparison of nuLnu needs; summed over the orders, the spectrum's nph,
+ * dn_dle and de_dle.  Needs the trace (GRM_OPT_TRACE_CAP > 0); the transport is untouched.
+ *
+ * grm_engine_cell_sums_accumulate bins the trace records [consumed, count) into an engine-owned
+ * device accumulator (allocated at the first call) and marks them consumed; *n_binned = the records
+ * it walked, *ms = the kernel's time (HIP events).  It fails (-1, grm_engine_last_error; accumulator
+ * and consumed mark untouched) with the trace off, and when the trace holds more records than its
+ * capacity -- records were lost; the message gives the count and the capacity.
+ * grm_engine_cell_sums_read copies the accumulator out (all zeros before the first accumulate);
+ * *n_skipped = recorded photons whose cell or order was out of range (0 in a good run).
+ * grm_engine_cell_sums_reset zeroes it.  grm_engine_reset zeroes it too, with the trace count and
+ * the consumed mark; changing GRM_OPT_TRACE_CAP marks every record counted so far as consumed.
+ * grm_engine_trace_rewind sets the trace count and the consumed mark to 0, so that a trace buffer
+ * sized for one track call serves a job of many; it fails while records are unconsumed (with the
+ * trace on): they would be dropped silently.
+ * grm_engine_cell_sums_device_ptr: the accumulator's device address (null before the first
+ * accumulate), for an in-place collective. */
+int grm_engine_cell_sums_accumulate(grm_engine *e, uint64_t *n_binned, double *ms);
+int grm_engine_cell_sums_read(grm_engine *e, double *out, uint64_t *n_skipped);
+int grm_engine_cell_sums_reset(grm_engine *e);
+int grm_engine_trace_rewind(grm_engine *e);
+void *grm_engine_cell_sums_device_ptr(grm_engine *e);
 /* copy a host batch into an engine-owned device buffer once (inputs resident in HBM); *dev_out is
  * valid for grm_engine_track_device until the next upload or destroy. */
 int grm_engine_upload(grm_engine *e, const grm_init_photon *batch, size_t n, grm_init_photon **dev_out);
@@ -379,6 +409,15 @@ int grm_write_spectrum(const grm_model *m, const grm_spectrum_cell *spectrum, co
  * log10(E) then, per theta bin, nph (recorded superphotons), dn_dle (sum w) and de_dle (sum w E),
  * "%.17g" -- what an effective-N / KS comparison of two spectra needs and the 37-column file lacks. */
 int grm_write_spectrum_stats(const grm_model *m, const grm_spectrum_cell *spectrum, const char *path);
+
+/* the spectrum by scattering order, from the cell sums [GRM_N_ORDERS][cells][GRM_N_CELL_SUMS]
+ * (grm_engine_cell_sums_read): a '#' header line, then 200 rows of log10(E) and, per theta bin and
+ * per order 0, 1, 2, >= 3, the three columns nuLnu, sigma_nuLnu and n, "%.17g" (1 + 6 * 4 * 3 = 73
+ * columns).  nuLnu = grm_write_spectrum's factor (me c^2 4 pi / dOmega / dlnE / Lsun) x sum wE;
+ * sigma_nuLnu = the same factor x sqrt(sum (wE)^2), the standard error of a sum of INDEPENDENT
+ * superphotons.  A scattered child is correlated with its parent (one family shares its history),
+ * which this estimate ignores: it is a lower bound where scattering families dominate a cell. */
+int grm_write_spectrum_orders(const grm_model *m, const double *sums, const char *path);
 
 /* ABI introspection: sizes of the POD structs (0 header 1 units 2 init_photon 3 spectrum_cell
  * 4 trace 5 stats 6 emit_zone) */

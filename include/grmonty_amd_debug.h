@@ -66,6 +66,10 @@ enum {
 /* which: see GRM_PROBE_* in DESIGN.md / csrc/grm_probe.hip. in/out are host arrays of
  * n * in_stride / n * out_stride doubles. */
 int grm_probe(grm_engine *e, int which, const double *in, int in_stride, double *out, int out_stride, size_t n);
+/* the cell-sum kernel (csrc/grm_cellsums.hip) on n host trace records: uploads them to a scratch
+ * buffer, bins them into a scratch accumulator and returns it in out[GRM_N_ORDERS][cells]
+ * [GRM_N_CELL_SUMS] and *n_skipped.  Touches neither the engine's trace nor its accumulator. */
+int grm_probe_cell_sums(grm_engine *e, const grm_trace *host_records, size_t n, double *out, uint64_t *n_skipped);
 
 #ifdef __cplusplus
 }
