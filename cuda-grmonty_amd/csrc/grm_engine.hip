@@ -1,6 +1,6 @@
 /*
- * grm_engine.hip -- persistent-wavefront superphoton transport for MI355X (gfx950)
- * and the C-ABI engine entry points (include/grmonty_amd.h).
+ * grm_engine.hip -- persistent-wavefront superphoton transport for MI355X (gfx950):
+ * the bulk kernel and the C-ABI engine entry points (include/grmonty_amd.h).
  *
  * Replaces the reference's 2-stream x 16384-slot lock-step pipeline of nine kernels
  * per geodesic step with host refills and host re-queueing of scattered photons
@@ -19,6 +19,12 @@
  * RNG: Philox4x32-10 stream per photon id (key = seed); a child's stream id is a
  * function of its parent's id and draw counter, so results do not depend on lane
  * assignment or scheduling (bias mode FROZEN makes a batch fully reproducible).
+ *
+ * This file holds the bulk kernel (transport_trip, record_stuck, track_kernel), the utility kernels
+ * (stash_kernel, job_counters_kernel, ctl_kernel with CtlOp) and the host engine with the C ABI.
+ * The device code the bulk kernel shares with the other transport kernels is grm_transport.h; the
+ * lone-photon kernels are grm_lone.hip (their two-wave pipeline: grm_lone_pipe.h), the role-split
+ * bulk kernel of variant builds is grm_split.hip.
  */
 #include <hip/hip_runtime.h>
 
@@ -32,1967 +38,12 @@
 
 #include <rccl/rccl.h>
 
-#include "grm_device.h"
+#include "grm_transport.h"
 #include "grm_cellsums.h"
 #include "grm_emit.h"
 
-using namespace grm;
-
 namespace {
 
-/* One workgroup per CU of 512 lanes: two waves per SIMD at 256 VGPRs each -- the second wave issues
- * while the first waits on a gather or a scalar/branch slot (+20% over one wave per SIMD, measured
- * on MI355X).  The per-lane state copies and per-step lane fields take the LDS, so the
- * spectrum goes to a per-workgroup slice in HBM (L2 atomics). */
-#define GRM_BLOCK 512
-constexpr int BLOCK = GRM_BLOCK;
-constexpr int MIN_WAVES_PER_SIMD = BLOCK / 256;
-constexpr int STACK_DEPTH = 16;                 /* scatter-request slots per lane ... */
-constexpr int WSTACK_CAP = 64 * STACK_DEPTH;    /* ... pooled into one stack per wave (192 KB of HBM) */
-
-/* 192-B scatter request (three aligned 64-B segments per request): the state at a scattering event from which the child
- * photon is sampled later (scatter_super_photon, harm_model.cpp:1071-1145).
- * Lane stacks and overflow pools hold these. */
-struct alignas(16) SReq {
-    double x[4], k[4];          /* parent position / wave vector at the scattering point */
-    double u_con[4], b_con[4];  /* fluid 4-velocity and b^mu there */
-    double b, theta_e;          /* |B| (Gauss), Theta_e there */
-    double w;                   /* child weight w_parent / bias */
-    double n_e_0, theta_e_0;
-    uint64_t id, parent;        /* child stream id, parent stream id */
-    int32_t n_scatt, pad0;
-};
-static_assert(sizeof(SReq) == 192, "SReq layout");
-
-/* 64-B per-lane cold photon fields (touched only at birth, scattering and recording): one aligned
- * segment per write.  The Photon fields l and e_0 (photon.hpp:19-36) are carried by the reference
- * but enter no result -- record_super_photon never accumulates e_0 and nothing reads l
- * (harm_model.cpp:1291-1335) -- so the lanes do not carry them. */
-struct alignas(16) Cold {
-    double e, x1i, x2i, n_e_0, theta_e_0, b_0;
-    uint64_t parent;
-    double pad;
-};
-static_assert(sizeof(Cold) == 64, "Cold layout");
-
-struct DevCounters {
-    unsigned long long n_recorded, n_scatt, max_tau_bits, n_steps;
-    unsigned long long n_tracked, n_children, n_overflow, n_dropped;
-    unsigned long long n_primaries, max_nstep, n_long, n_abandoned, abort, n_nan;
-    unsigned long long karg_bad; /* track_kernel's kernel-argument check failed (see kargs_check) */
-    /* a multi-rank job's warm-up state of this rank for the others' admission gates (pass blocks
-     * only, see warm_job): photons admitted << 32 + photons in flight (signed), WARM_DONE once the
-     * rank's admission is over */
-    unsigned long long warm;
-};
-static_assert(sizeof(DevCounters) == 16 * 8, "DevCounters layout (grm_engine_debug_counters)");
-constexpr unsigned long long WARM_DONE = 1ull << 63, WARM_HIST = 1ull << 32;
-/* set by the rank's transport launch as it starts (the job's start barrier, job_started) */
-constexpr unsigned long long WARM_STARTED = 1ull << 62;
-
-
-struct LoneRec;
-struct Ctl {
-    const void *pool;      /* grm_init_photon[] (kind 0) or SReq[] (kind 1) */
-    int pool_kind;
-    unsigned long long n_pool;
-    unsigned long long *pool_head;
-    /* claim order: the head counts claim positions; position q < pos_end holds pool photon
-     * (q mod 2^pool_sh) * pool_m + q / 2^pool_sh (a hole when that is >= n_pool).  Primaries are
-     * interleaved over 2^pool_sh evenly spaced runs of the zone-ordered batch (see run_transport) */
-    unsigned long long pos_end, pool_m;
-    int pool_sh;
-    uint64_t id_base;
-    uint32_t key0, key1;
-    SReq *stack;           /* [lanes][STACK_DEPTH] */
-    Cold *cold;            /* [lanes] */
-    SReq *ovf;             /* overflow out */
-    unsigned long long ovf_cap;
-    unsigned long long *ovf_count;
-    grm_spectrum_cell *spec;
-    double *spec_blocks;   /* [grid][SPEC_LDS] per-workgroup spectrum slices (when not in LDS), kept zero */
-    DevCounters *ctr;
-    grm_trace *trace;
-    unsigned long long trace_cap;
-    unsigned long long *trace_count;
-    int bias_frozen;
-    double f_scatt, f_rec, f_maxtau;
-    unsigned long long *timing; /* GRM_TIMING builds: per-region wave cycles */
-    int refill_min;             /* idle lanes a wave gathers before it takes primaries */
-    int child_min;              /* children a wave gathers (on its stack and idle lanes) per sampling batch */
-    /* Live-bias warm-up inside the launch: the first admit_n pool photons go in batches, each
-     * admitted only when everything started before it (children included) has ended, and as large
-     * as the history behind it (64, 64, 128, 256, ...): bias_func's running counters then evolve as
-     * in the serial reference (harm_model.cpp:1391-1404).  *admit_end = end of the admitted batch
-     * (~0 = no limit), *in_flight = photons started and not ended (children counted when pushed). */
-    unsigned long long admit_n, admit_h0, admit_lim;
-    int admit_slack;
-    unsigned long long admit_b0; /* first batch */
-    unsigned long long admit_spread; /* photons one wave claims at most per warm-up claim (0: no cap) */
-    unsigned long long *admit_end, *in_flight;
-    unsigned long long *waves;  /* per-wave record of the launch: start, exit (s_memrealtime), trips, photons */
-    unsigned long long *phases; /* s_memrealtime when the warm-up admission ended ([0]) and the pool's
-                                 * last claim chunk was taken ([1]); null = not recorded */
-    int lanes;
-    /* watchdog: a launch older than watchdog_ticks (s_memrealtime, 100 MHz; 0 = off) abandons its
-     * photons and exits, so no input can keep the GPU busy without bound.  The first stuck_cap
-     * abandoned lanes leave a STUCK_WORDS-double record (grm_engine_debug_stuck). */
-    unsigned long long watchdog_ticks;
-    double *stuck;
-    unsigned long long stuck_cap, *stuck_count;
-    /* lone photons handed over to lone_kernel (null = never); lone_all: every photon is handed over
-     * at the top of its first step (GRM_OPT_LONE = 2: tests of the lone path) */
-    LoneRec *lone;
-    unsigned long long lone_cap, *lone_count;
-    int lone_all;
-    /* early hand-over of long photons to the concurrent early_kernel (early_q null = off): a photon
-     * of >= early_steps steps at the top of a step; slots claimed by *early_tail, published by
-     * early_ready[slot] = early_tag; *wg_exit counts exited workgroups, the last sets *early_done;
-     * *early_live: 1 once early_kernel runs (no hand-over before, so none can strand), 2 when it
-     * closed the queue because the bulk launch had not started (kernels serialised, e.g. under a
-     * counter profiler); *bulk_live: set by every bulk workgroup as it starts */
-    LoneRec *early_q;
-    unsigned long long *early_ready, early_cap, early_tag;
-    unsigned long long *early_tail, *early_head, *early_done, *wg_exit, *early_live, *bulk_live;
-    int early_steps;
-    /* a multi-rank pass's warm-up waits at most this long (s_memrealtime ticks, 100 MHz) for every
-     * peer's launch of the pass to start before its first claim (0: no wait; GRM_OPT_JOB_START_WAIT_MS) */
-    unsigned long long start_wait_ticks;
-    int karg_test; /* test only (GRM_OPT_KARG_TEST): the kernel-argument check expects lanes + this */
-    /* The job's bias counters across ranks: peers[r] = rank r's array of per-pass counter blocks
-     * (its own included; remote ones mapped over xGMI by IPC), ctr_slot = this pass's block.  With
-     * n_peers > 1 bias_func's running counters are the whole job's: the sums of n_scatt and
-     * n_recorded and the max of max tau_scatt over the ranks' blocks of this pass. */
-    const DevCounters *const *peers;
-    int n_peers, ctr_slot;
-    /* split_kernel (grm_split.hip): an interaction wave runs its block once split_thr / 64 of its
-     * active lanes have a step ready, or after split_spin short sleeps */
-    int split_thr, split_spin;
-    int split_gthr; /* a geometry wave pushes once split_gthr / 64 of its live lanes can (or after split_spin sleeps) */
-    int split_mode; /* 1: waves 0-3 geometry, 4-7 interaction; 2: roles by the SIMD a wave runs on */
-    int split_batch; /* consecutive ready slots an interaction lane may evaluate per round */
-    /* the early worker's own children (GRM_OPT_EARLY_CHILDREN): a scattering on a pair appends the
-     * child's scatter request to the early queue (LoneRec::pad = 1, queue_child_push), where the next
-     * free pair sets it up and tracks it (child_setup_body); *early_fin counts the queue slots
-     * finished -- tracked, or given up by a pair that left -- and *early_kids the children appended */
-    int early_kids_on;
-    unsigned long long *early_fin, *early_kids;
-    /* the lone kernel's own children (the same option): a scattering on a lone pair appends the child's
-     * request to lk_q (lk_tail; published by lk_ready[slot] = lk_tag), which the pairs that have
-     * finished their photon take in order (lk_taken); lk_active counts the pairs tracking a photon
-     * and lk_standby those waiting for a child (at most LK_STANDBY wait; the rest leave) */
-    int lk_on;
-    LoneRec *lk_q;
-    unsigned long long *lk_ready, lk_cap, lk_tag;
-    unsigned long long *lk_tail, *lk_taken, *lk_active, *lk_standby;
-    unsigned long long *lk_orig; /* handed-over photons whose pair has finished them */
-};
-constexpr int STUCK_WORDS = 16, STUCK_CAP = 256;
-constexpr unsigned REFRESH_TRIPS = 64; /* counter flush + bias refresh + watchdog period (power of 2) */
-
-/* Per-step (or rarer) lane fields: an LDS column per lane ([field][lane], conflict-free), read and
- * written where used -- what brings the kernel's register demand under the 256 VGPRs two waves per
- * SIMD allow. */
-#define GRM_LANE_XFIELDS(X)                                                                          \
-    X(tau_abs, 0) X(tau_scatt, 1) X(alpha_scatti, 2) X(alpha_absi, 3) X(bi, 4) X(fl_ne, 5)          \
-    X(ph2_e0s, 6)     /* photon_2's e_0_s (its x^1..3, k, dk are in the ph2 LDS slot) */              \
-    X(p_dtau_abs, 7) X(p_dtau_scatt, 8) X(p_wc, 9) /* carried across the re-push */
-constexpr int LANE_XFIELDS = 10;
-#define GRM_LANE_IFIELDS(X)                                                                          \
-    X(n_scatt, 0)                                                                                    \
-    X(flight, 1) /* warm-up: photons started (+) / ended (-) since the last flush */                \
-    /* the lane's launch counters (widened and wave-reduced at exit) */                              \
-    X(c_tracked, 2) X(c_primaries, 3) X(c_children, 4) X(c_nstep_max, 5) X(c_long, 6)
-constexpr int LANE_IFIELDS = 7;
-/* [field][lane], indexed with threadIdx.x so that every access is one ds_read/ds_write_b64 with an
- * immediate offset (a generic pointer here would turn them into FLAT accesses, which also count in
- * vmcnt and cost a 64-bit address register each) */
-__shared__ double s_lanex[LANE_XFIELDS * GRM_BLOCK];
-/* volatile (the compiler must not keep the fields in registers across trips -- the point is to free
- * them) and typed in the LDS address space (a generic volatile access becomes FLAT + vmcnt waits) */
-typedef __attribute__((address_space(3))) volatile double LdsDouble;
-__shared__ int s_lanei[LANE_IFIELDS * GRM_BLOCK];
-typedef __attribute__((address_space(3))) volatile int LdsInt;
-
-/* hot photon state: lives in VGPRs (and, see above, LDS) for the photon's whole life */
-struct Lane {
-    double x[4], k[4], dk[4];
-    double w, e_0_s;
-    int n_step;
-    Rng rng;
-    /* per-trip push state machine: phase 0 = loop top, 1 = geodesic step in progress,
-     * 2 = re-push to the scattering point in progress; depth/pend = position in the halving tree */
-    int phase, depth;
-    uint32_t pend;
-    double dl, hlen;                      /* step size of this iteration; length being pushed */
-#define X(name, i) \
-    __device__ __forceinline__ LdsDouble &name() const { return ((LdsDouble *)s_lanex)[(i) * GRM_BLOCK + threadIdx.x]; }
-#define XI(name, i) \
-    __device__ __forceinline__ LdsInt &name() const { return ((LdsInt *)s_lanei)[(i) * GRM_BLOCK + threadIdx.x]; }
-    GRM_LANE_XFIELDS(X)
-    GRM_LANE_IFIELDS(XI)
-#undef X
-#undef XI
-};
-
-/* Denominator of bias_func's first term, bias_norm * max_tau_scatt * (<N_scatt> + 2)
- * (harm_model.cpp:1391-1404).  Wave-uniform: computed once per refresh at a converged point of the
- * lane loop from the frozen snapshot or from the live device counters -- the live counters sit in
- * device-coherent memory (every XCD adds to them), so loading them per step would put a
- * cross-die round trip on every interaction. */
-__device__ __forceinline__ double bias_den(const Params &P, const Ctl &C) {
-    double scatt, rec, mts;
-    if (C.bias_frozen) {
-        scatt = C.f_scatt;
-        rec = C.f_rec;
-        mts = C.f_maxtau;
-    } else if (C.n_peers > 1) {
-        /* the job's counters: lane r reads rank r's block of this pass (one remote round trip for
-         * the wave, every REFRESH_TRIPS trips), then a wave reduction (converged callers only) */
-        const int lane = (int)(threadIdx.x & 63);
-        unsigned long long sc = 0, rc = 0, mt = 0;
-        if (lane < C.n_peers) {
-            const DevCounters *pc = C.peers[lane] + C.ctr_slot;
-            sc = __hip_atomic_load(&pc->n_scatt, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
-            rc = __hip_atomic_load(&pc->n_recorded, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
-            mt = __hip_atomic_load(&pc->max_tau_bits, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
-        }
-#pragma unroll
-        for (int o = 32; o > 0; o >>= 1) {
-            sc += __shfl_xor(sc, o);
-            rc += __shfl_xor(rc, o);
-            mt = max(mt, (unsigned long long)__shfl_xor(mt, o));
-        }
-        scatt = (double)sc;
-        rec = (double)rc;
-        mts = __longlong_as_double((long long)mt);
-    } else { /* live, reference-like adaptive bias */
-        scatt = (double)__hip_atomic_load(&C.ctr->n_scatt, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        rec = (double)__hip_atomic_load(&C.ctr->n_recorded, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        mts = __longlong_as_double(
-            (long long)__hip_atomic_load(&C.ctr->max_tau_bits, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT));
-    }
-    const double avg = scatt / (1.0 * rec + 1.0);
-    const long long d = __double_as_longlong(P.bias_norm * mts * (avg + 2.0));
-    const int lo = __builtin_amdgcn_readfirstlane((int)(d & 0xffffffffll));
-    const int hi = __builtin_amdgcn_readfirstlane((int)(d >> 32));
-    return __longlong_as_double(((long long)hi << 32) | (unsigned int)lo);
-}
-
-/* The job's warm-up state across ranks (n_peers > 1): photons admitted and photons in flight,
- * summed over the ranks' blocks of this pass (DevCounters::warm; lane r reads rank r's).  A rank
- * whose admission is over no longer counts its flight (its waves stop reporting ends), a rank that
- * has not started the pass reads zero.  Converged callers only. */
-__device__ __forceinline__ void warm_job(const Ctl &C, unsigned long long &hist, long long &flight) {
-    const int lane = (int)(threadIdx.x & 63);
-    unsigned long long h = 0;
-    long long f = 0;
-    if (lane < C.n_peers) {
-        const unsigned long long v =
-            __hip_atomic_load(&(C.peers[lane] + C.ctr_slot)->warm, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
-        const unsigned long long r = v & ~(WARM_DONE | WARM_STARTED);
-        h = (r + (WARM_HIST >> 1)) >> 32; /* flight may be negative between a claim and its undo */
-        f = (v & WARM_DONE) ? 0 : (long long)(r - h * WARM_HIST);
-    }
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) {
-        h += __shfl_xor(h, o);
-        f += __shfl_xor(f, o);
-    }
-    hist = h;
-    flight = f < 0 ? 0 : f;
-}
-
-/* The job's start barrier (n_peers > 1): has every rank's transport launch of this pass started
- * (WARM_STARTED in its pass block)?  A rank that began its warm-up before the others' launches were
- * resident -- a launch queued behind other work, or on the one-GPU emulation behind the other ranks'
- * emission -- would admit the job's first batches alone and run its bulk on a history the job never
- * had.  Converged callers only. */
-__device__ __forceinline__ bool job_started(const Ctl &C) {
-    const int lane = (int)(threadIdx.x & 63);
-    bool ok = true;
-    if (lane < C.n_peers)
-        ok = (__hip_atomic_load(&(C.peers[lane] + C.ctr_slot)->warm, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM) &
-              WARM_STARTED) != 0;
-    return __ballot(!ok) == 0;
-}
-
-/* bias_func (harm_model.cpp:1391-1404), same expression and rounding as the reference */
-__device__ __forceinline__ double bias_func(double den, double t_e, double w) {
-    /* the constant divisions as multiplications by the rounded reciprocal (<= 1 ulp; an IEEE divide
-     * is 11 VALU ops and these run every step) */
-    const double max = w * (0.5 / WEIGHT_MIN);
-    double bias = fdiv(100.0 * t_e * t_e, den);
-    if (bias < TP_OVER_TE) bias = TP_OVER_TE;
-    if (bias > max) bias = max;
-    return bias * (1.0 / TP_OVER_TE);
-}
-
-/* Diagnostic build (-DGRM_TIMING): per-wave cycle attribution with s_memtime stamps, accumulated in
- * LDS by the first active lane.  Slots: 0 child refill+sampling, 1 pool refill+init, 2 transport
- * trip, 3 loop total, 4 trips, 5 trips with a child sampled, 6 trips with an init, 7 bias refresh,
- * 8 phase-0 block, 9 push attempt, 10 restore / halving bookkeeping, 11 fluid gather,
- * 12 radiation + bias, 13 rest of the interaction, 14 refill decision and claims (the loop top to
- * the refill loads); 15 = last stamp.  Never built into the product. */
-#ifdef GRM_TIMING
-__shared__ unsigned long long g_tlds[GRM_BLOCK / 64][24];
-__device__ __forceinline__ void tstamp(int r) {
-    const unsigned long long t = __builtin_amdgcn_s_memtime();
-    const unsigned long long ex = __ballot(1);
-    const int w = threadIdx.x >> 6;
-    if ((int)(threadIdx.x & 63) == __ffsll((long long)ex) - 1) {
-        g_tlds[w][r] += t - g_tlds[w][15];
-        g_tlds[w][15] = t;
-    }
-}
-#define TSTAMP(r) tstamp(r)
-#define TCOUNT(r) do { if ((threadIdx.x & 63) == 0) g_tlds[threadIdx.x >> 6][r] += 1; } while (0)
-/* lane occupancy of a block: slot r counts executions, r + 1 the lanes in them (divergent callers) */
-#define TLANES(r, pred)                                                                            \
-    do {                                                                                           \
-        const unsigned long long b_ = __ballot(pred);                                              \
-        if (b_ && (int)(threadIdx.x & 63) == __ffsll((long long)__ballot(1)) - 1) {               \
-            g_tlds[threadIdx.x >> 6][r] += 1;                                                      \
-            g_tlds[threadIdx.x >> 6][(r) + 1] += __popcll(b_);                                     \
-        }                                                                                          \
-    } while (0)
-#else
-#define TSTAMP(r) do { } while (0)
-#define TCOUNT(r) do { } while (0)
-#define TLANES(r, pred) do { } while (0)
-#endif
-
-/* stop_criterion (harm_model.cpp:1589-1616) */
-__device__ __forceinline__ bool stop_criterion(const Params &P, double x1, double &w, Rng &rng) {
-    if (x1 < P.x1_min) return true;
-    if (x1 > P.x1_max) {
-        if (w < WEIGHT_MIN) {
-            if (uniform(rng) <= 1.0 / ROULETTE)
-                w *= ROULETTE;
-            else
-                w = 0.0;
-        }
-        return true;
-    }
-    if (w < WEIGHT_MIN) {
-        if (uniform(rng) <= 1.0 / ROULETTE) {
-            w *= ROULETTE;
-        } else {
-            w = 0.0;
-            return true;
-        }
-    }
-    return false;
-}
-
-__device__ __forceinline__ bool stop_criterion(const Params &P, Lane &L) { return stop_criterion(P, L.x[1], L.w, L.rng); }
-
-__device__ void write_trace(const Ctl &C, const Cold *cold, uint64_t id, double w, double x1, double x2,
-                                         double x3, double tau_abs, double tau_scatt, int n_scatt, int n_step,
-                                         int reason, int ix2, int i_e) {
-    const unsigned long long t = atomicAdd(C.trace_count, 1ull);
-    if (t >= C.trace_cap) return;
-    grm_trace &r = C.trace[t];
-    r.id = id;
-    r.parent_id = cold ? cold->parent : ~0ull;
-    r.w = w;
-    r.e = cold ? cold->e : 0.0;
-    r.x1 = x1;
-    r.x2 = x2;
-    r.x3 = x3;
-    r.tau_abs = tau_abs;
-    r.tau_scatt = tau_scatt;
-    r.n_scatt = n_scatt;
-    r.n_step = n_step;
-    r.end_reason = reason;
-    r.ix2 = ix2;
-    r.i_e = i_e;
-    r.pad_ = 0;
-}
-
-__device__ __forceinline__ void trace_end(const Ctl &C, const Cold *cold, const Lane &L, int reason) {
-    if (C.trace)
-        write_trace(C, cold, L.rng.id, L.w, L.x[1], L.x[2], L.x[3], L.tau_abs(), L.tau_scatt(), L.n_scatt(), L.n_step,
-                    reason, -1, -1);
-}
-
-/* Workgroup-private spectrum slice in HBM and per-wave counter deltas in LDS.  The block adds its
- * slice to the global spectrum once, at exit; counter deltas are flushed by each wave at its
- * bias-refresh points.  Field f of a cell = field f of grm_spectrum_cell (e_0, never accumulated, is
- * left out); a slice cell is padded to 16 doubles = 128 B, so one record's twelve adds are two
- * aligned 64-B segments.
- *
- * Records are not added one by one.  An fp64 atomic add executes at the memory side (it leaves L2
- * as a 64-B request, MI355X_MICROARCH.md "Global float atomics"), and a no-return atomic stays
- * counted in vmcnt for ~1-3 k cycles: a record's twelve single-lane atomics cost twelve fabric
- * requests, and the wave's next wait for a load of its own (the zone gather) waited for them too.
- * record_super_photon here writes the record's twelve addends into a per-wave LDS buffer
- * (RECBUF_N records); at a converged point of the lane loop a wave with RECBUF_FLUSH or more
- * buffered records adds them with the whole wave, one lane per (record, field): 16 records in 3
- * wave-instructions, ~2 requests per record.  A buffer found full falls back to the direct adds. */
-constexpr int SPEC_FIELDS = 12;
-constexpr int SPEC_CELL = 16;                              /* padded slice cell (doubles) */
-constexpr int SPEC_LDS = N_TH_BINS * N_E_BINS * SPEC_CELL; /* doubles per slice */
-__device__ __forceinline__ double *spec_slice(const Ctl &C) { return C.spec_blocks + (size_t)blockIdx.x * SPEC_LDS; }
-constexpr int RECBUF_N = 16, RECBUF_FLUSH = 8;
-/* the waves that record (all of a track_kernel / lone workgroup; the interaction waves of the split
- * kernel, grm_split.hip) and a wave's index among them */
-#ifndef GRM_REC_WAVES
-#define GRM_REC_WAVES (GRM_BLOCK / 64)
-#define GRM_REC_WAVE(t) ((t) >> 6)
-#endif
-__shared__ double s_recv[GRM_REC_WAVES][RECBUF_N * SPEC_FIELDS]; /* per-wave record addends */
-__shared__ int s_recc[GRM_REC_WAVES][RECBUF_N];                   /* their slice cells */
-__shared__ int s_recn[GRM_REC_WAVES];                             /* records buffered */
-__shared__ unsigned long long s_cnt[GRM_REC_WAVES][4]; /* n_recorded, n_scatt, max tau bits, max flushed */
-
-__device__ __forceinline__ void flush_counters(const Ctl &C) {
-    if ((threadIdx.x & 63) == 0) {
-        unsigned long long *c = s_cnt[GRM_REC_WAVE(threadIdx.x)];
-        if (c[0]) {
-            atomicAdd(&C.ctr->n_recorded, c[0]);
-            c[0] = 0;
-        }
-        if (c[1]) {
-            atomicAdd(&C.ctr->n_scatt, c[1]);
-            c[1] = 0;
-        }
-        if (c[2] > c[3]) {
-            atomicMax(&C.ctr->max_tau_bits, c[2]);
-            c[3] = c[2];
-        }
-    }
-}
-
-/* record_super_photon (harm_model.cpp:1291-1335).  cell_stride == SPEC_CELL: into the wave's record
- * buffer (track_kernel; spec = the workgroup's slice for the fallback); else twelve direct adds
- * into spec (the global spectrum, lone / early kernels) */
-__device__ void record_photon(const Params &P, const Ctl &C, const Cold *cold, uint64_t id, double w, double x1,
-                              double x2, double x3, double tau_abs, double tau_scatt, int n_scatt, int n_step,
-                              double *spec, int cell_stride) {
-    int ix2 = -1, i_e = -1, reason = 1;
-    const double e = cold->e;
-    if (!(isnan(w) || isnan(e))) {
-        unsigned long long *cnt = s_cnt[GRM_REC_WAVE(threadIdx.x)];
-        atomicMax(cnt + 2, (unsigned long long)__double_as_longlong(tau_scatt)); /* tau_scatt >= 0 */
-        if (x2 < 0.5 * (P.xs2 + P.xe2))
-            ix2 = (int)(x2 / P.th_dx2);
-        else
-            ix2 = (int)((P.xe2 - x2) / P.th_dx2);
-        if (ix2 >= 0 && ix2 < N_TH_BINS) {
-            i_e = (int)((flog(e) - P.spec_l_e_0) / SPEC_D_L_E + 2.5) - 2;
-            if (i_e >= 0 && i_e < N_E_BINS) {
-                reason = 0;
-                atomicAdd(cnt + 0, 1ull);
-                atomicAdd(cnt + 1, (unsigned long long)n_scatt);
-                const int cell = ix2 * N_E_BINS + i_e;
-                double *s = spec + cell * cell_stride;
-                const double x1i = cold->x1i, x2i = cold->x2i;
-                int slot = RECBUF_N;
-                if (cell_stride == SPEC_CELL) {
-                    const int wv = GRM_REC_WAVE(threadIdx.x);
-                    slot = atomicAdd(&s_recn[wv], 1);
-                    if (slot < RECBUF_N) {
-                        double *b = &s_recv[wv][slot * SPEC_FIELDS];
-                        b[0] = w;
-                        b[1] = w * e;
-                        b[2] = 1.0;
-                        b[3] = (double)n_scatt;
-                        b[4] = w * x1i;
-                        b[5] = w * (x2i * x2i);
-                        b[6] = w * (x3 * x3);
-                        b[7] = w * tau_abs;
-                        b[8] = w * tau_scatt;
-                        b[9] = w * cold->n_e_0;
-                        b[10] = w * cold->theta_e_0;
-                        b[11] = w * cold->b_0;
-                        s_recc[wv][slot] = cell;
-                    }
-                }
-                if (slot >= RECBUF_N) {
-                atomicAdd(s + 0, w);                      /* dn_dle */
-                atomicAdd(s + 1, w * e);                  /* de_dle */
-                atomicAdd(s + 2, 1.0);                    /* nph */
-                atomicAdd(s + 3, (double)n_scatt);        /* nscatt */
-                atomicAdd(s + 4, w * x1i);                /* x1i_av */
-                atomicAdd(s + 5, w * (x2i * x2i));        /* x2i_sq */
-                atomicAdd(s + 6, w * (x3 * x3));          /* x3f_sq */
-                atomicAdd(s + 7, w * tau_abs);            /* tau_abs */
-                atomicAdd(s + 8, w * tau_scatt);          /* tau_scatt */
-                atomicAdd(s + 9, w * cold->n_e_0);        /* ne_0 */
-                atomicAdd(s + 10, w * cold->theta_e_0);   /* theta_e_0 */
-                atomicAdd(s + 11, w * cold->b_0);         /* b_0 */
-                }
-            } else {
-                i_e = -1;
-            }
-        } else {
-            ix2 = -1;
-        }
-    }
-    if (C.trace)
-        write_trace(C, cold, id, w, x1, x2, x3, tau_abs, tau_scatt, n_scatt, n_step, reason, ix2, i_e);
-}
-
-__device__ __forceinline__ void end_of_life(const Params &P, const Ctl &C, const Cold *cold, const Lane &L) {
-    /* record_criterion (harm_model.cpp:1618) && n_step <= max_n_step (:1066) */
-    if (L.x[1] > P.x1_max && L.n_step <= MAX_N_STEP)
-        record_photon(P, C, cold, L.rng.id, L.w, L.x[1], L.x[2], L.x[3], L.tau_abs(), L.tau_scatt(), L.n_scatt(), L.n_step,
-                      spec_slice(C), SPEC_CELL);
-    else
-        trace_end(C, cold, L, 2);
-}
-
-/* the wave's buffered records into the workgroup's slice: lane j adds field j % 12 of record j / 12
- * (called by the whole wave at a converged point) */
-__device__ __forceinline__ void flush_records(const Ctl &C) {
-    const int wv = GRM_REC_WAVE(threadIdx.x), lane = threadIdx.x & 63;
-    const int n = min(__builtin_amdgcn_readfirstlane(s_recn[wv]), RECBUF_N);
-    double *slice = spec_slice(C);
-    for (int j = lane; j < n * SPEC_FIELDS; j += 64) {
-        const int r = j / SPEC_FIELDS, f = j - r * SPEC_FIELDS;
-        atomicAdd(slice + s_recc[wv][r] * SPEC_CELL + f, s_recv[wv][j]);
-    }
-    if (lane == 0) s_recn[wv] = 0;
-}
-
-/* emitted photon -> lane (harm_model.cpp:373-391); n_scatt = 0 is the caller's */
-__device__ __forceinline__ void load_primary_core(const Ctl &C, uint64_t idx, Rng &rng, double x[4], double k[4],
-                                                  double &w, Cold *cold) {
-    const double2 *s = reinterpret_cast<const double2 *>(reinterpret_cast<const grm_init_photon *>(C.pool) + idx);
-    double2 v[7]; /* x, k, w, e, l, n_e_0, theta_e_0, b_0 (e_0 and n_scatt = 0 are not needed) */
-#pragma unroll
-    for (int q = 0; q < 7; ++q) v[q] = s[q];
-    x[0] = v[0].x; x[1] = v[0].y; x[2] = v[1].x; x[3] = v[1].y;
-    k[0] = v[2].x; k[1] = v[2].y; k[2] = v[3].x; k[3] = v[3].y;
-    w = v[4].x;
-    rng.id = C.id_base + idx;
-    rng.ctr = 0;
-    rng.ctr_hi = 0;
-    Cold c;
-    c.e = v[4].y;
-    c.x1i = x[1];
-    c.x2i = x[2];
-    c.n_e_0 = v[5].y;
-    c.theta_e_0 = v[6].x;
-    c.b_0 = v[6].y;
-    c.parent = ~0ull;
-    c.pad = 0.0;
-    *cold = c;
-}
-
-__device__ __forceinline__ void load_primary(const Ctl &C, uint64_t idx, Lane &L, Cold *cold) {
-    load_primary_core(C, idx, L.rng, L.x, L.k, L.w, cold);
-    L.n_scatt() = 0;
-}
-
-/* scatter request -> child photon in the lane (scatter_super_photon after its first
- * validity check, harm_model.cpp:1083-1144, with sample_scattered_photon :1147-1215).
- * false = child invalid (k_tetrad out of range or NaN). */
-__device__ __forceinline__ bool sample_child_core(const Params &P, const SReq &R, Rng &rng, double x[4], double k[4],
-                                                  double &w, Cold *cold) {
-    rng.id = R.id;
-    rng.ctr = 0;
-    rng.ctr_hi = 0;
-    w = R.w;
-#pragma unroll
-    for (int i = 0; i < 4; ++i) x[i] = R.x[i];
-    Cold c;
-    c.x1i = R.x[1];
-    c.x2i = R.x[2];
-    c.n_e_0 = R.n_e_0;
-    c.theta_e_0 = R.theta_e_0;
-    c.b_0 = R.b;
-    c.parent = R.parent;
-    c.e = 0.0;
-    c.pad = 0.0;
-    Trig T;
-    trig_at(P, R.x, T);
-    Gcov G;
-    gcov_from_trig(P, T, G);
-    double bh[4];
-    if (R.b > 0.0) {
-        const double s = R.b / P.b_unit;
-#pragma unroll
-        for (int i = 0; i < 4; ++i) bh[i] = R.b_con[i] / s;
-    } else {
-        bh[0] = 0.0; bh[1] = 1.0; bh[2] = 0.0; bh[3] = 0.0;
-    }
-    double ec[4][4];
-    make_tetrad(R.u_con, bh, G, ec);
-    double kt[4];
-#pragma unroll
-    for (int i = 0; i < 4; ++i) {
-        double el[4];
-        tetrad_cov_row(ec, G, i, el);
-        kt[i] = el[0] * R.k[0] + el[1] * R.k[1] + el[2] * R.k[2] + el[3] * R.k[3];
-    }
-    bool ok = !(kt[0] > 1.0e5 || kt[0] < 0.0 || isnan(kt[1]));
-    if (ok) {
-        double p[4], ktp[4];
-        sample_electron(rng, kt, p, R.theta_e);
-        sample_scattered(rng, kt, p, ktp);
-#pragma unroll
-        for (int i = 0; i < 4; ++i) k[i] = ec[0][i] * ktp[0] + ec[1][i] * ktp[1] + ec[2][i] * ktp[2] + ec[3][i] * ktp[3];
-        ok = !isnan(k[1]);
-        if (ok) {
-            /* e_cov^T (-k0', k1', k2', k3'): only component 0 is needed (e; l enters no result) */
-            ktp[0] = -ktp[0];
-            double t0 = 0.0;
-#pragma unroll
-            for (int j = 0; j < 4; ++j) {
-                double el[4];
-                tetrad_cov_row(ec, G, j, el);
-                t0 += el[0] * ktp[j];
-            }
-            c.e = -t0;
-        }
-    }
-    *cold = c;
-    return ok;
-}
-
-__device__ bool sample_child(const Params &P, const Ctl &C, const SReq &R, Lane &L, Cold *cold) {
-    L.n_scatt() = R.n_scatt;
-    return sample_child_core(P, R, L.rng, L.x, L.k, L.w, cold);
-}
-
-__device__ __forceinline__ void load_sreq(const SReq *src, SReq &R) {
-    const double2 *s = reinterpret_cast<const double2 *>(src);
-    double2 *d = reinterpret_cast<double2 *>(&R);
-#pragma unroll
-    for (int q = 0; q < 12; ++q) d[q] = s[q];
-}
-
-__device__ __forceinline__ void store_sreq(SReq *dst, const SReq &R) {
-    const double2 *s = reinterpret_cast<const double2 *>(&R);
-    double2 *d = reinterpret_cast<double2 *>(dst);
-#pragma unroll
-    for (int q = 0; q < 12; ++q) d[q] = s[q];
-}
-
-/* the scatter request of a scattered photon's child (scatter_super_photon's inputs, :1071-1145) */
-__device__ __forceinline__ void make_sreq(SReq &R, const double x[4], const double k[4], const Rng &rng, int n_scatt,
-                                          const Cold *cold, const Fluid &F, double wc) {
-#pragma unroll
-    for (int i = 0; i < 4; ++i) {
-        /* x^0 (Boyer-Lindquist time) enters no result -- not the metric (stationary), the fluid, the
-         * record or any test -- so the device does not carry it: children start at x^0 = 0 */
-        R.x[i] = i == 0 ? 0.0 : x[i];
-        R.k[i] = k[i];
-        R.u_con[i] = F.u_con[i];
-        R.b_con[i] = F.b_con[i];
-    }
-    R.b = F.b;
-    R.theta_e = F.theta_e;
-    R.w = wc;
-    R.n_e_0 = cold->n_e_0;
-    R.theta_e_0 = cold->theta_e_0;
-    R.id = child_id(rng.id, rng.ctr);
-    R.parent = rng.id;
-    R.n_scatt = n_scatt + 1;
-    R.pad0 = 0;
-}
-
-/* append to the overflow pool (tracked by the next launch) */
-__device__ __forceinline__ void push_overflow_req(const Ctl &C, const SReq &R) {
-    const unsigned long long o = atomicAdd(C.ovf_count, 1ull);
-    if (o < C.ovf_cap)
-        store_sreq(C.ovf + o, R);
-    else
-        atomicAdd(&C.ctr->n_dropped, 1ull);
-    atomicAdd(&C.ctr->n_overflow, 1ull);
-}
-
-/* push the scattered photon's child out as a scatter request: onto the wave's stack (HBM entries,
- * top counter in LDS), else the overflow pool (tracked by the next launch).  true = on the stack */
-__device__ __forceinline__ bool push_request(const Ctl &C, const double x[4], const double k[4], const Rng &rng,
-                                             int n_scatt, const Cold *cold, const Fluid &F, double wc, SReq *wstack,
-                                             int *wtop) {
-    SReq R;
-    make_sreq(R, x, k, rng, n_scatt, cold, F, wc);
-    const int slot = atomicAdd(wtop, 1); /* LDS; values past the cap are clamped at the next refill */
-    if (slot < WSTACK_CAP) {
-        store_sreq(wstack + slot, R);
-        return true;
-    }
-    push_overflow_req(C, R);
-    return false;
-}
-
-/* Two per-lane state copies live in LDS ([slot][lane], conflict-free 8-B words), 11 slots each:
- * x^1..x^3, k, dk/dlambda; photon_2's e_0_s is a lane field.
- *   ph2: photon_2 (harm_model.cpp:920-925), also the depth-0 backup of push_photon;
- *   bk:  the backup of push_photon at depth > 0 (x_cpy/k_cpy/dk_cpy, :1222-1228).
- * 2 x 11 x 8 B x 512 lanes = 88 KB (+ 40 KB of lane fields, 16 KB of lane ints): no global memory
- * traffic on the halving path. */
-constexpr int LDS_DOUBLES_PER_LANE = 11;
-#ifndef GRM_WARM_BLOCKS
-#define GRM_WARM_BLOCKS 64
-#endif
-#ifndef GRM_WARM_WAVES
-#define GRM_WARM_WAVES 8
-#endif
-constexpr unsigned WARM_BLOCKS = GRM_WARM_BLOCKS; /* workgroups that take the warm-up's admission batches */
-constexpr unsigned WARM_WAVES = GRM_WARM_WAVES;   /* ... and their waves that do (waves 0-3: one per SIMD) */
-constexpr unsigned PHASE_LOG = 64;   /* words of the launch's phase log (after the per-wave record) */
-constexpr unsigned long long RES_CHUNK = 64; /* claim positions a wave reserves per pool-head atomic */
-/* The launch-control words (grm_engine::d_small: pool head, in-flight, admission end, hand-over and
- * early-worker words) one per SMALL_STRIDE words, each in a cache line of its own: the warm-up's
- * CAS / atomics on the pool head and the in-flight count, the parked waves' polls of the admission
- * end and the early worker's queue words would otherwise all queue on one 128-B line */
-#ifndef GRM_SMALL_STRIDE
-#define GRM_SMALL_STRIDE 32
-#endif
-constexpr int SMALL_STRIDE = GRM_SMALL_STRIDE;
-/* waves parked during the warm-up poll the admission end once per PARK_SLEEPS x s_sleep(127) */
-#ifndef GRM_PARK_SLEEPS
-#define GRM_PARK_SLEEPS 1
-#endif
-
-__device__ __forceinline__ void save_xkdk(const Slot &s, const Lane &L) {
-#pragma unroll
-    for (int i = 0; i < 3; ++i) s[i] = L.x[1 + i];
-#pragma unroll
-    for (int i = 0; i < 4; ++i) {
-        s[3 + i] = L.k[i];
-        s[7 + i] = L.dk[i];
-    }
-}
-
-__device__ __forceinline__ void load_xkdk(const Slot &s, Lane &L) {
-#pragma unroll
-    for (int i = 0; i < 3; ++i) L.x[1 + i] = s[i];
-#pragma unroll
-    for (int i = 0; i < 4; ++i) {
-        L.k[i] = s[3 + i];
-        L.dk[i] = s[7 + i];
-    }
-}
-
-__device__ __forceinline__ void store_ph2(const Slot &ph2, Lane &L) {
-    L.ph2_e0s() = L.e_0_s;
-    save_xkdk(ph2, L);
-}
-
-__device__ __forceinline__ void load_ph2(const Slot &ph2, Lane &L) {
-    load_xkdk(ph2, L);
-}
-
-/* photon set-up at the head of track_super_photon (harm_model.cpp:895-917).  Here only the validity
- * check and the counters; the rest -- fluid and absorption/scattering coefficients at x, bias, and
- * dk/dlambda from the connection at x (init_dkdlam) -- runs on the lane's next trip as phase 3,
- * inside the same push and fluid/radiation code the stepping lanes execute (see transport_trip), so
- * a refill costs a few loads instead of a divergent block of its own.  false = invalid. */
-__device__ bool init_photon(const Ctl &C, const Cold *cold, Lane &L, const Slot &ph2) {
-    if (isnan(L.x[0]) || isnan(L.x[1]) || isnan(L.x[2]) || isnan(L.x[3]) || isnan(L.k[0]) || isnan(L.k[1]) ||
-        isnan(L.k[2]) || isnan(L.k[3]) || L.w == 0.0) {
-        L.n_step = 0; /* the trace record is this photon's, not the lane's last one */
-        L.tau_abs() = L.tau_scatt() = 0.0;
-        trace_end(C, cold, L, 4);
-        return false;
-    }
-#pragma unroll
-    for (int i = 0; i < 4; ++i) L.dk[i] = 0.0;
-    store_ph2(ph2, L); /* x, k kept here across the set-up's zero-length push */
-    L.n_step = 0;
-    L.tau_abs() = L.tau_scatt() = 0.0;
-    L.e_0_s = cold->e;
-    L.hlen = 0.0;
-    L.depth = 0;
-    L.pend = 0;
-    L.phase = 3;
-    return true;
-}
-
-/* Head of a geodesic step (phase 0): stop test, photon_2, step size (harm_model.cpp:919-927).
- * false = the photon's life ended. */
-__device__ __forceinline__ bool trip_begin(const Params &P, const Ctl &C, Lane &L, Cold *cold, const Slot &ph2) {
-    if (stop_criterion(P, L)) {
-        end_of_life(P, C, cold, L);
-        return false;
-    }
-    /* photon_2 (:920-925) -- also the depth-0 backup of the push */
-    store_ph2(ph2, L);
-    L.dl = step_size(P, L.x, L.k);
-    L.hlen = L.dl;
-    L.depth = 0;
-    L.pend = 0;
-    L.phase = 1;
-    return true;
-}
-
-/* lane `src`'s value of v (src wave-uniform) */
-__device__ __forceinline__ double bcast(double v, int src) {
-    const long long b = __double_as_longlong(v);
-    const int lo = __builtin_amdgcn_readlane((int)b, src), hi = __builtin_amdgcn_readlane((int)(b >> 32), src);
-    return __longlong_as_double(((long long)hi << 32) | (unsigned int)lo);
-}
-
-/* Tail speculation.  A wave whose only work left is ONE photon (the pool is drained and its stack
- * empty) completes that photon's current push -- push_photon's halving recursion,
- * harm_model.cpp:1217-1289 -- with all its lanes: from the start state of every sub-step the owner
- * attempts depth d and idle lane r attempts depth d + r, at once.  The serial walk would attempt d,
- * then (restored to the same start state) d + 1, ... until one passes or depth MAX_SUBDIV accepts
- * whatever it gets; each of these attempts is made here from bit-identical inputs, so the shallowest
- * accepted one IS the serial walk's sub-step, its failed shallower attempts become the pending
- * second halves they would have left, and the walk goes on from the accepted state.  One round per
- * accepted sub-step instead of one trip per attempt: the photons that halve to depth 7 on every
- * step (255 attempts for 128 sub-steps) -- the last photons of a pass -- run ~2x faster.
- * Called by the whole wave (converged); `owner` is wave-uniform.  Every lane's copy of the push
- * state (x, k, dk/dlambda, e_0_s, hlen, depth, pend) follows the owner's; only the owner's is used. */
-/* The halving walk proper, on a push state every lane of the wave holds identically (x, k, dk/dlambda,
- * e_0_s; the node `depth` of the halving tree being pushed, the pending second halves `pend`); lane
- * rank r (0 for the state's owner) attempts depth + r.  Leaves the completed push in every lane. */
-/* QUAD: the lone geometry wave's form -- quad r of lanes attempts depth + r with the quad-parallel
- * push (push_attempt_quad), rank = lane / 4 (16 ranks still cover every depth to MAX_SUBDIV) */
-template <bool QUAD = false>
-__device__ __forceinline__ int walk_push(const Params &P, double x[4], double k[4], double dk[4], double &e_0_s,
-                                         double hlen, int depth, uint32_t pend, int rank, int owner) {
-    int rounds = 0; /* attempt rounds (diagnostics) */
-    while (true) {
-        if (!(x[1] < P.xs1) && depth == MAX_SUBDIV) {
-            /* a leaf of the deepest level is accepted whatever its checks say (:1279): every lane makes
-             * that one attempt from the identical state, so no lane has to win and be broadcast (the
-             * second halves at depth MAX_SUBDIV -- every other round of a photon that halves to full
-             * depth, seed 124's tail in round 4) */
-            double e_1;
-            Trig T;
-            Gcov G;
-            if (QUAD)
-                push_attempt_quad(P, x, k, dk, e_0_s, ldexp(hlen, -MAX_SUBDIV), e_1, T, G, (int)(threadIdx.x & 3));
-            else
-                push_attempt(P, x, k, dk, e_0_s, ldexp(hlen, -MAX_SUBDIV), e_1, T, G);
-            e_0_s = e_1;
-            ++rounds;
-        } else if (!(x[1] < P.xs1)) {
-            /* every lane attempts in place from the same start state; the winner's result is then
-             * broadcast over all of them */
-            const int d = depth + rank;
-            double e_1 = 0.0;
-            bool ok = false;
-            if (d <= MAX_SUBDIV) {
-                Trig T;
-                Gcov G;
-                const bool fail = QUAD ? push_attempt_quad(P, x, k, dk, e_0_s, ldexp(hlen, -d), e_1, T, G,
-                                                              (int)(threadIdx.x & 3))
-                                       : push_attempt(P, x, k, dk, e_0_s, ldexp(hlen, -d), e_1, T, G);
-                ok = !fail || d == MAX_SUBDIV;
-            }
-            /* the owner's attempt if it passed, else the shallowest passing helper (helper depth grows
-             * with lane index); some lane passes, since 63 helpers cover every depth to MAX_SUBDIV */
-            const unsigned long long acc = __ballot(ok);
-            ++rounds;
-            const int w = ((acc >> owner) & 1ull) ? owner : __ffsll((long long)acc) - 1;
-            const int dw = __builtin_amdgcn_readlane(d, w);
-#pragma unroll
-            for (int i = 0; i < 4; ++i) {
-                x[i] = bcast(x[i], w);
-                k[i] = bcast(k[i], w);
-                dk[i] = bcast(dk[i], w);
-            }
-            e_0_s = bcast(e_1, w);
-            pend |= ((2u << dw) - 1u) & ~((2u << depth) - 1u); /* second halves at depths depth+1..dw */
-            depth = dw;
-        }
-        if (pend == 0) break;
-        depth = 31 - __builtin_clz(pend);
-        pend &= ~(1u << depth);
-    }
-    return rounds;
-}
-
-__device__ __forceinline__ int walk_rank(int owner) {
-    const int lane = (int)(threadIdx.x & 63);
-    return lane == owner ? 0 : (lane < owner ? lane + 1 : lane);
-}
-
-/* complete the owner's push in progress (phase 1 or 2, any node of its halving tree) with the wave */
-__device__ __forceinline__ void halving_walk(const Params &P, Lane &L, int owner) {
-#pragma unroll
-    for (int i = 0; i < 4; ++i) {
-        L.x[i] = bcast(L.x[i], owner);
-        L.k[i] = bcast(L.k[i], owner);
-        L.dk[i] = bcast(L.dk[i], owner);
-    }
-    L.e_0_s = bcast(L.e_0_s, owner);
-    const double hlen = bcast(L.hlen, owner);
-    const int depth = __builtin_amdgcn_readlane(L.depth, owner);
-    const uint32_t pend = (uint32_t)__builtin_amdgcn_readlane((int)L.pend, owner);
-    walk_push(P, L.x, L.k, L.dk, L.e_0_s, hlen, depth, pend, walk_rank(owner), owner);
-    L.depth = 0;
-    L.pend = 0;
-}
-
-/* Lone photons.  When a wave's only work left is one photon (the pool is drained, its stack empty),
- * that photon's latency is the pass's tail: such photons run for 1e5-1e6 steps (trapped
- * near-circular orbits, polar Zeno stepping, full-depth halving -- all exact reference semantics,
- * which end them only at max_n_step, harm_model.cpp:1058-1063).  The lane loop is the wrong place
- * for them (one lane of 64 busy, per-trip refill logic, lane fields in LDS): the wave hands the
- * photon over (export_lone, at the top of a step) and exits, and after the launch lone_kernel runs
- * every handed-over photon with a whole wave of its own: straight-line steps of
- * track_super_photon's loop (:919-1063) with the state in registers, every lane holding the same
- * values, the pushes as halving walks over the lanes (walk_push), only lane 0 writing.  Its
- * scattered children go to the overflow pool, which the host relaunches the lane loop over. */
-struct alignas(16) LoneRec {
-    double x[4], k[4], dk[4];
-    double w, e_0_s;
-    double tau_abs, tau_scatt, a_si, a_ai, bi, fl_ne;
-    Cold c;
-    uint64_t id;
-    uint32_t ctr;
-    int32_t n_step, n_scatt, pad;
-};
-static_assert(sizeof(LoneRec) == 256, "LoneRec layout");
-static_assert(sizeof(SReq) <= offsetof(LoneRec, pad), "an early-queue slot holds a scatter request below its pad word");
-
-__device__ __forceinline__ void export_lone(LoneRec *r, const Lane &L, const Cold *cold) {
-    /* field by field (a LoneRec built in registers first would add 68 VGPRs at this point of the loop) */
-    double2 *d = reinterpret_cast<double2 *>(r);
-    d[0] = make_double2(L.x[0], L.x[1]);
-    d[1] = make_double2(L.x[2], L.x[3]);
-    d[2] = make_double2(L.k[0], L.k[1]);
-    d[3] = make_double2(L.k[2], L.k[3]);
-    d[4] = make_double2(L.dk[0], L.dk[1]);
-    d[5] = make_double2(L.dk[2], L.dk[3]);
-    d[6] = make_double2(L.w, L.e_0_s);
-    d[7] = make_double2(L.tau_abs(), L.tau_scatt());
-    d[8] = make_double2(L.alpha_scatti(), L.alpha_absi());
-    d[9] = make_double2(L.bi(), L.fl_ne());
-    const double2 *c = reinterpret_cast<const double2 *>(cold);
-#pragma unroll
-    for (int q = 0; q < 4; ++q) d[10 + q] = c[q];
-    r->id = L.rng.id;
-    r->ctr = L.rng.ctr;
-    r->n_step = L.n_step;
-    r->n_scatt = L.n_scatt();
-    r->pad = 0;
-}
-
-/* the child of a lone photon's scattering, straight to the overflow pool */
-__device__ __forceinline__ void push_overflow(const Ctl &C, const double x[4], const double k[4], const Rng &rng,
-                                              int n_scatt, const Cold *cold, const Fluid &F, double wc) {
-    SReq R;
-    make_sreq(R, x, k, rng, n_scatt, cold, F, wc);
-    push_overflow_req(C, R);
-}
-
-/* the child of an early-worker photon's scattering (lane 0): its scatter request goes into a slot of
- * the early queue, marked as a request (LoneRec::pad = 1; the SReq fills the slot's first 192 B), and
- * the next free pair of the worker sets it up and tracks it at once (child_setup_body), as the
- * reference tracks a child as soon as it is made (harm_model.cpp:1016-1023); the overflow pool when
- * the queue is full.  A slot claimed past the cap is never published, as in the lane loop's
- * hand-over. */
-/* kids: 1 the early worker's queue, 2 the lone kernel's (lk_q; its slots are all requests) */
-__device__ __forceinline__ void queue_child_push(const Ctl &C, int kids, const double x[4], const double k[4],
-                                                 const Rng &rng, int n_scatt, const Cold *cold, const Fluid &F,
-                                                 double wc) {
-    SReq R;
-    make_sreq(R, x, k, rng, n_scatt, cold, F, wc);
-    LoneRec *q = kids == 1 ? C.early_q : C.lk_q;
-    unsigned long long *ready = kids == 1 ? C.early_ready : C.lk_ready;
-    unsigned long long *tail = kids == 1 ? C.early_tail : C.lk_tail;
-    const unsigned long long cap = kids == 1 ? C.early_cap : C.lk_cap, tag = kids == 1 ? C.early_tag : C.lk_tag;
-    if (__hip_atomic_load(tail, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) < cap) {
-        const unsigned long long slot = atomicAdd(tail, 1ull);
-        if (slot < cap) {
-            LoneRec *r = q + slot;
-            store_sreq(reinterpret_cast<SReq *>(r), R);
-            r->pad = 1;
-            if (kids == 1) atomicAdd(C.early_kids, 1ull);
-            __threadfence();
-            __hip_atomic_store(ready + slot, tag, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_AGENT);
-            return;
-        }
-    }
-    push_overflow_req(C, R);
-}
-
-/* Two waves per handed-over photon, pipelined: the geometry wave (wave 1) runs the photon's
- * geodesic ahead -- photon_2, step size, push as a halving walk over its lanes (:920-930) -- into a
- * ring of LONE_RING steps in LDS; the interaction wave (wave 0) consumes them in order and does
- * everything else of the loop body: the stop criteria with their roulette draws, fluid, absorption
- * and scattering coefficients, bias, the scattering decision, the weight (:919, :932-1063).  The
- * geodesic does not depend on the interactions except at a scattering, where the photon continues
- * from photon_2 pushed to the scattering point (:1005-1010): the interaction wave makes that push
- * itself and restarts the geometry wave from it (a new generation; steps of the old one are
- * discarded by their tag).  Both halves of a step then run at once on two SIMDs. */
-constexpr int LONE_RING = 32, LONE_BATCH = 16;
-constexpr unsigned long long LONE_STOP = ~0ull;
-struct alignas(16) LoneSlot {
-    double out[13], dl;     /* the state after the push (x, k, dk/dlambda, e_0_s) and the step size */
-    unsigned long long tag; /* (generation << 32) | (step index + 1), stored last */
-};
-struct alignas(16) LoneCtl {
-    double rs[13];                /* restart state: photon_2 of the generation's first step */
-    unsigned long long cons, req; /* steps consumed; restart request (generation << 32 | step) or LONE_STOP */
-};
-/* one photon's two-wave pipeline state (a geometry wave + an interaction wave) */
-struct LonePair {
-    LoneSlot ring[LONE_RING];
-    LoneCtl ctl;
-};
-constexpr int LONE_PAIRS = 2; /* pairs of the concurrent worker (early_kernel: 4 waves, one per SIMD, up to 512 VGPRs) */
-/* early_kernel dispatches its geometry waves to s_pair[0] / s_pair[1] by a constant index (one inlined
- * copy per pair): more pairs need more arms there, or a pair's interaction wave waits forever */
-static_assert(LONE_PAIRS == 2, "early_kernel's geometry dispatch assumes two pairs");
-/* early_kernel waits this long (s_memrealtime, 100 MHz) for the bulk launch to start before it
- * takes the launches for serialised and leaves */
-constexpr unsigned long long EARLY_ALONE_TICKS = 100000; /* 1 ms */
-__shared__ LonePair s_pair[LONE_PAIRS];
-
-__device__ __forceinline__ void pack13(double *d, const double x[4], const double k[4], const double dk[4],
-                                       double e) {
-#pragma unroll
-    for (int i = 0; i < 4; ++i) {
-        d[i] = x[i];
-        d[4 + i] = k[i];
-        d[8 + i] = dk[i];
-    }
-    d[12] = e;
-}
-
-__device__ __forceinline__ void unpack13(const double *d, double x[4], double k[4], double dk[4], double &e) {
-#pragma unroll
-    for (int i = 0; i < 4; ++i) {
-        x[i] = d[i];
-        k[i] = d[4 + i];
-        dk[i] = d[8 + i];
-    }
-    e = d[12];
-}
-
-/* A kernel argument read afresh where it is used.  The arguments (Params, Ctl: ~0.7 KB) are
- * loop-invariant, so the compiler loads them once at entry and keeps them live across the persistent
- * loop; they do not fit the SGPR file, and the overflow is spilled into VGPR lanes and read back with
- * v_readlane -- a VALU instruction (plus hazard nops) per use, inside the step.  Passing the argument
- * block through an opaque SGPR copy at the top of each trip makes every use a scalar load from the
- * kernarg segment instead (constant address space: s_load, scalar cache, no VALU issue). */
-/* The kernarg segment of track_kernel / lone_kernel / early_kernel, all (Params, Ctl): explicit
- * arguments in order at their ABI alignment, i.e. the layout of this struct.  Two traps: the address
- * of a by-value kernel parameter is NOT the kernarg segment (taking it makes the compiler copy the
- * parameter into private memory), and __builtin_amdgcn_kernarg_segment_ptr() is only meaningful in
- * the kernel itself (in a called function it lowers to null): only the kernel takes the pointer
- * (kargs()).  Used by track_kernel only: in the lone pipeline's serial chain the exposed scalar-load
- * latency costs more than the readlanes (lone probe 1.80 vs 1.63 us/step, profiles/r02q_karg_ab.txt). */
-struct KArgs {
-    Params P;
-    Ctl C;
-};
-static_assert(offsetof(KArgs, C) == sizeof(Params), "kernarg layout: Ctl follows Params");
-typedef const KArgs __attribute__((address_space(4))) KArgsK;
-/* call only in the body of a kernel whose explicit arguments are exactly (Params, Ctl) */
-__device__ __forceinline__ KArgsK *kargs() { return (KArgsK *)__builtin_amdgcn_kernarg_segment_ptr(); }
-/* the kernarg segment through an opaque scalar copy of its pointer: loads through it cannot be
- * hoisted out of the loop the copy is made in */
-__device__ __forceinline__ KArgsK *karg_fresh(KArgsK *ka) {
-    /* (a non-inlined function receives ka in VGPRs: make it scalar first; a no-op in a kernel) */
-    const uint64_t a = (uint64_t)ka;
-    KArgsK *k = (KArgsK *)(((uint64_t)(uint32_t)__builtin_amdgcn_readfirstlane((int)(uint32_t)(a >> 32)) << 32) |
-                           (uint32_t)__builtin_amdgcn_readfirstlane((int)(uint32_t)a));
-    asm volatile("" : "+s"(k));
-    return k;
-}
-__device__ __forceinline__ const Params &karg_params(KArgsK *k) { return *(const Params *)&k->P; }
-__device__ __forceinline__ const Ctl &karg_ctl(KArgsK *k) { return *(const Ctl *)&k->C; }
-/* Guard of the kernarg-segment reads: the words the loop reads through kargs() must be the launch's
- * arguments.  Compares, at the ends and in the middle of both blocks, the segment's words with the
- * by-value parameters (which the compiler reads from the segment by its own ABI).  A layout the
- * struct KArgs does not describe (a compiler or ABI change) makes this fail for every wave, and the
- * launch then exits at once with DevCounters::karg_bad set, which the host turns into an error
- * (run_passes): there is no silent wrong-argument mode.  Wave-uniform (scalar loads only). */
-__device__ __forceinline__ bool kargs_check(KArgsK *ka, const Params &P, const Ctl &C) {
-    const Params &kp = karg_params(ka);
-    const Ctl &kc = karg_ctl(ka);
-    bool ok = kp.n1 == P.n1 && kp.n2 == P.n2 && __double_as_longlong(kp.a) == __double_as_longlong(P.a) &&
-              __double_as_longlong(kp.bias_norm) == __double_as_longlong(P.bias_norm) && kp.zones == P.zones &&
-              kp.k2 == P.k2;
-    ok = ok && kc.pool == C.pool && kc.n_pool == C.n_pool && kc.ctr == C.ctr && kc.key0 == C.key0 &&
-         kc.spec_blocks == C.spec_blocks && kc.watchdog_ticks == C.watchdog_ticks && kc.lanes == C.lanes + C.karg_test &&
-         kc.early_steps == C.early_steps;
-    return __builtin_amdgcn_readfirstlane((int)ok) != 0;
-}
-
-/* The push's uniform inputs for the geometry wave's loop, held in VGPRs.  The lone kernels take
- * (Params, Ctl) by value; the ~0.7 KB of arguments do not fit the SGPR file next to the interaction
- * wave's code, so the compiler spills them into lanes of a VGPR and reloads each use with a
- * v_readlane (a VALU instruction, plus hazard nops before the SGPR is read): 1,118 such reloads in
- * lone_kernel, dozens of them inside one push.  Copies made lane-varying by an empty asm live in
- * VGPR pairs instead (26 VGPRs of the 512 a single wave per SIMD has) and feed the fp64 VALU
- * directly.  Same values, same operations. */
-__device__ __forceinline__ void push_params_vgpr(Params &G) {
-    asm volatile("" : "+v"(G.a), "+v"(G.a2), "+v"(G.a3), "+v"(G.a4), "+v"(G.r0), "+v"(G.hs1), "+v"(G.hs1_pi));
-    asm volatile("" : "+v"(G.th_fac), "+v"(G.d2k), "+v"(G.m2a), "+v"(G.xe2), "+v"(G.xs1));
-}
-
-constexpr bool GEO_QUAD = true; /* the geometry wave pushes with quad-parallel corrector rows (§4.2:
-                                   * the plain push 1.41-1.42 us/step against 1.36-1.37, s3e) */
-
-/* The geometry wave of a pair (see above): runs photon after photon -- each begins as a restart
- * request from the interaction wave -- until LONE_STOP. */
-__device__ void lone_geometry(const Params &P_, const Ctl &C, int lane, LonePair &pr) {
-    Params P = P_;
-    push_params_vgpr(P);
-    unsigned gen = 0;
-    unsigned long long p = 0, cur = 0, cons = 0; /* cons: the last value read of pr.ctl.cons */
-    bool spec = false; /* speculate the halving depths on this step's push (the last one halved) */
-    double x[4], k[4], dk[4], e_0_s;
-    {
-        /* a photon starts as a restart (generation, step 0) from its hand-over state in rs */
-        unsigned long long r0;
-        while ((r0 = __hip_atomic_load(&pr.ctl.req, __ATOMIC_ACQUIRE, __HIP_MEMORY_SCOPE_WORKGROUP)) == 0)
-            __builtin_amdgcn_s_sleep(2);
-        if (r0 == LONE_STOP) return;
-        cur = r0;
-        gen = (unsigned)(r0 >> 32);
-        p = r0 & 0xffffffffull;
-        cons = p;
-        unpack13(pr.ctl.rs, x, k, dk, e_0_s);
-    }
-    const double *ph2src = pr.ctl.rs; /* where the current step's start state (photon_2) is kept */
-#ifdef GRM_TIMING
-    unsigned long long g_last = __builtin_amdgcn_s_memtime();
-    unsigned long long tg[6] = {0, 0, 0, 0, 0, 0}; /* steps, rounds, walk, step size, rest, halved */
-#endif
-    while (true) {
-        if (p + 1 >= cons + LONE_RING) { /* the slot of step p and that of p - 1 must be consumed */
-            cons = __hip_atomic_load(&pr.ctl.cons, __ATOMIC_ACQUIRE, __HIP_MEMORY_SCOPE_WORKGROUP);
-            if (p + 1 >= cons + LONE_RING) {
-#ifdef GRM_TIMING
-                const unsigned long long t0 = __builtin_amdgcn_s_memtime();
-                __builtin_amdgcn_s_sleep(1); /* the ring is full */
-                if (lane == 0) atomicAdd(C.timing + 31, __builtin_amdgcn_s_memtime() - t0);
-#else
-                __builtin_amdgcn_s_sleep(1); /* the ring is full */
-#endif
-                if (__hip_atomic_load(&pr.ctl.req, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP) == cur) continue;
-            }
-        }
-        /* the restart request (stop folded in as LONE_STOP): read once per step and looked at
-         * after the push, so that its LDS latency hides behind it; a step computed while a
-         * restart was pending is dropped (and one published just before a restart carries the
-         * old generation's tag, which the interaction wave skips) */
-        const unsigned long long req = __hip_atomic_load(&pr.ctl.req, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
-#ifdef GRM_TIMING
-        const unsigned long long g0 = __builtin_amdgcn_s_memtime();
-#endif
-        const double dl = step_size(P, x, k);
-#ifdef GRM_TIMING
-        const unsigned long long g1 = __builtin_amdgcn_s_memtime();
-#endif
-        /* Most steps pass their first attempt: then every lane makes that same attempt, the
-         * state stays identical over the wave and needs no broadcast.  A step that halves
-         * continues as a halving walk, and the next step speculates from the start. */
-        int rounds = 1;
-        {
-            if (!spec) {
-                bool fail = false;
-                if (!(x[1] < P.xs1)) {
-                    double e_1;
-                    Trig T;
-                    Gcov G;
-                    /* every quad of lanes makes the attempt, lane q contracting connection row q */
-                    fail = GEO_QUAD ? push_attempt_quad(P, x, k, dk, e_0_s, dl, e_1, T, G, lane & 3)
-                                    : push_attempt(P, x, k, dk, e_0_s, dl, e_1, T, G);
-                    if (fail) { /* depth 0 failed: the serial walk goes on at depth 1 (:1279-1285) */
-                        /* from the step's start state, photon_2: the slot published last (or the
-                         * generation's restart state) -- no register copy on every step for the ~2 %
-                         * that fail (the copy cost ~24 moves per step of the serial chain) */
-                        double e_r;
-                        unpack13(ph2src, x, k, dk, e_r);
-                        rounds += walk_push<GEO_QUAD>(P, x, k, dk, e_0_s, dl, 1, 2u, GEO_QUAD ? lane >> 2 : lane, 0);
-                    } else {
-                        e_0_s = e_1;
-                    }
-                }
-                spec = fail;
-            } else {
-                rounds = walk_push<GEO_QUAD>(P, x, k, dk, e_0_s, dl, 0, 0u, GEO_QUAD ? lane >> 2 : lane, 0);
-                spec = rounds > 1;
-            }
-        }
-        if (req != cur) {
-            if (req == LONE_STOP) {
-#ifdef GRM_TIMING
-                /* slots 16-21: photons of > 1e5 steps (the tail), 22-27: the others */
-                if (lane == 0)
-                    for (int r = 0; r < 6; ++r) atomicAdd(C.timing + (tg[0] > 100000 ? 16 : 22) + r, tg[r]);
-#endif
-                break;
-            }
-            /* restart from the scattering point (this step, if computed, is on the old geodesic) */
-            __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup"); /* rs was written before req */
-            cur = req;
-            gen = (unsigned)(req >> 32);
-            p = req & 0xffffffffull;
-            cons = p; /* what the interaction wave has consumed when it requests a restart at p */
-            unpack13(pr.ctl.rs, x, k, dk, e_0_s);
-            ph2src = pr.ctl.rs;
-            spec = false;
-            continue;
-        }
-#ifdef GRM_TIMING
-        const unsigned long long g2 = __builtin_amdgcn_s_memtime();
-        tg[0] += 1;
-        tg[1] += (unsigned long long)rounds;
-        tg[2] += g2 - g1;
-        tg[3] += g1 - g0;
-        tg[4] += g0 - g_last;
-        tg[5] += spec ? 1ull : 0ull;
-        g_last = g2;
-#endif
-        if (lane == 0) {
-            LoneSlot &S = pr.ring[p % LONE_RING];
-            pack13(S.out, x, k, dk, e_0_s);
-            S.dl = dl;
-            /* LDS operations of a wave complete in order: the slot is written before its tag
-             * (a compiler barrier keeps the stores in program order; no wait for completion) */
-            __asm__ volatile("" ::: "memory");
-            __hip_atomic_store(&S.tag, ((unsigned long long)gen << 32) | (p + 1), __ATOMIC_RELAXED,
-                               __HIP_MEMORY_SCOPE_WORKGROUP);
-        }
-        ph2src = pr.ring[p % LONE_RING].out; /* lane 0's stores precede this wave's later loads */
-        ++p;
-    }
-}
-
-/* The draws of a lone photon come from a window of 64 consecutive Philox counters evaluated at once
- * (lane i: counter wbase + i; the same block and bits as uniform(), so the same numbers in the same
- * order): a serial draw is then two v_readlane instead of a 10-round Philox chain. */
-__device__ __forceinline__ double lone_draw(Rng &rng, double &win, uint32_t &wbase, int lane) {
-    if (rng.ctr - wbase >= 64u) { /* wave-uniform */
-        wbase = rng.ctr;
-        Rng g = rng;
-        g.ctr = wbase + (uint32_t)lane;
-        win = uniform(g);
-    }
-    const double u = bcast(win, (int)(rng.ctr - wbase));
-    ++rng.ctr;
-    return u;
-}
-
-/* stop_criterion (harm_model.cpp:1589-1616) with the windowed draws */
-__device__ __forceinline__ bool lone_stop(const Params &P, double x1, double &w, Rng &rng, double &win,
-                                          uint32_t &wbase, int lane) {
-    if (x1 < P.x1_min) return true;
-    if (x1 > P.x1_max) {
-        if (w < WEIGHT_MIN) {
-            if (lone_draw(rng, win, wbase, lane) <= 1.0 / ROULETTE)
-                w *= ROULETTE;
-            else
-                w = 0.0;
-        }
-        return true;
-    }
-    if (w < WEIGHT_MIN) {
-        if (lone_draw(rng, win, wbase, lane) <= 1.0 / ROULETTE) {
-            w *= ROULETTE;
-        } else {
-            w = 0.0;
-            return true;
-        }
-    }
-    return false;
-}
-
-/* The interaction wave of a pair: one handed-over photon, from its record to its end (the
- * geometry wave is started on it with a restart request: generation gen + 1, step 0). */
-/* kids: where the photon's scattered children go -- 0 the overflow pool, 1 the early worker's queue,
- * 2 the lone kernel's (queue_child_push) */
-__device__ void lone_interact(const Params &P, const Ctl &C, const LoneRec &R, int lane, LonePair &pr, unsigned &gen_io,
-                              int kids) {
-    double x1 = R.x[1];
-    unsigned gen = gen_io + 1;
-    if (lane == 0) {
-        double x[4], k[4], dk[4];
-#pragma unroll
-        for (int i = 0; i < 4; ++i) {
-            x[i] = R.x[i];
-            k[i] = R.k[i];
-            dk[i] = R.dk[i];
-        }
-        pack13(pr.ctl.rs, x, k, dk, R.e_0_s); /* the state before step 0 */
-        pr.ctl.cons = 0;
-        __hip_atomic_store(&pr.ctl.req, (unsigned long long)gen << 32, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_WORKGROUP);
-    }
-    const bool own = lane == 0;
-    const int rank = lane;
-    double w = R.w;
-    double tau_abs = R.tau_abs, tau_scatt = R.tau_scatt, a_si = R.a_si, a_ai = R.a_ai, bi = R.bi, fl_ne = R.fl_ne;
-    const Cold *cold = &R.c;
-    int n_step = R.n_step;
-    const int n_scatt = R.n_scatt;
-    Rng rng;
-    rng.k0 = C.key0;
-    rng.k1 = C.key1;
-    rng.id = R.id;
-    rng.ctr = R.ctr;
-    rng.ctr_hi = 0;
-    double win = 0.0;
-    uint32_t wbase = rng.ctr - 64u; /* empty window */
-    double bias_d = bias_den(P, C);
-    const unsigned long long rt_start = __builtin_amdgcn_s_memrealtime();
-    unsigned long long steps = 0, children = 0;
-    bool ended = false, abandoned = false;
-    int reason = -1; /* ended without a record: trace reason */
-    unsigned long long gen_start = 0; /* the generation's first step */
-    unsigned long long si = 0;        /* index of the next step */
-    /* the step whose end state is the photon's state (LONE_STOP: the restart state in rs) */
-    unsigned long long cur = LONE_STOP;
-    unsigned since = 0; /* steps since the last counter flush / bias refresh / watchdog look */
-    bool done = false;
-#ifdef GRM_TIMING
-    unsigned long long ti[4] = {0, 0, 0, 0}; /* batches, steps in them, batch-evaluation cycles, serial cycles */
-#endif
-    while (!done) {
-        /* A batch: the consecutive steps the geometry wave has ready (at least one, at most
-         * LONE_BATCH).  Lane j evaluates step si + j at once: the fluid and the absorption /
-         * scattering coefficients at its end point (these depend on the geodesic only), and from
-         * them -- taking the previous step's coefficients from lane j - 1, as the serial recurrence
-         * has them whenever step j interacts -- its optical depths, the weight factor of a step
-         * without scattering and the weight-independent part of bias_func.  The steps then run in
-         * order, each taking its lane's values; a scattering discards the rest of the batch (the
-         * photon continues elsewhere). */
-        if (since >= REFRESH_TRIPS) { /* at a batch boundary, so that bias_d is fixed over a batch */
-            since = 0;
-            flush_counters(C);
-            if (!C.bias_frozen) bias_d = bias_den(P, C);
-            if (C.watchdog_ticks) {
-                bool stop = __hip_atomic_load(&C.ctr->abort, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) != 0;
-                if (!stop && __builtin_amdgcn_s_memrealtime() - rt_start > C.watchdog_ticks) {
-                    stop = true;
-                    if (own) __hip_atomic_store(&C.ctr->abort, 1ull, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-                }
-                if (stop) {
-                    abandoned = true;
-                    break;
-                }
-            }
-        }
-        const unsigned long long base = si;
-        {
-            LoneSlot &S0 = pr.ring[base % LONE_RING];
-            const unsigned long long want = ((unsigned long long)gen << 32) | (base + 1);
-#ifdef GRM_TIMING
-            const unsigned long long tw0 = __builtin_amdgcn_s_memtime();
-#endif
-            while (__hip_atomic_load(&S0.tag, __ATOMIC_ACQUIRE, __HIP_MEMORY_SCOPE_WORKGROUP) != want)
-                __builtin_amdgcn_s_sleep(1);
-#ifdef GRM_TIMING
-            if (own) atomicAdd(C.timing + 30, __builtin_amdgcn_s_memtime() - tw0);
-#endif
-        }
-        const unsigned long long qj = base + (lane < LONE_BATCH ? lane : 0);
-        const bool ready = lane < LONE_BATCH && __hip_atomic_load(&pr.ring[qj % LONE_RING].tag, __ATOMIC_ACQUIRE,
-                                                                  __HIP_MEMORY_SCOPE_WORKGROUP) ==
-                                                    (((unsigned long long)gen << 32) | (qj + 1));
-        const unsigned long long rb = __ballot(ready);
-        const int nb = rb == ~0ull ? 64 : __ffsll((long long)~rb) - 1; /* leading run of ready steps (>= 1) */
-#ifdef GRM_TIMING
-        const unsigned long long tb0 = __builtin_amdgcn_s_memtime();
-#endif
-        double l_x1, l_ne, l_as = 0.0, l_aa = 0.0, l_dts, l_dta, l_b0, l_fac;
-        int l_zero;
-        {
-            const LoneSlot &Sj = pr.ring[(base + (lane < nb ? lane : 0)) % LONE_RING];
-            double xj[4], kj[4], dkj[4], ej;
-            unpack13(Sj.out, xj, kj, dkj, ej);
-            const double dl = Sj.dl;
-            Trig T;
-            Gcov G;
-            ZoneFetch Z;
-            zone_fetch(P, xj, Z);
-            trig_at(P, xj, T);
-            gcov_from_trig(P, T, G);
-            Fluid F;
-            fluid_from(P, xj, G, Z, F);
-            const double nu = fluid_nu(kj, F);
-            l_zero = (nu < 0.0 || F.n_e == 0.0) ? 1 : 0; /* bound_flag (:941-955) or nu < 0 */
-            if (!l_zero) radiation_coeffs(P, kj, F, nu, l_as, l_aa);
-            l_x1 = xj[1];
-            l_ne = F.n_e;
-            /* the coefficients the step starts from: the step before's (lane j - 1), or the carried
-             * (the shuffles outside the conditional: with lane 0 masked off, lane 1 would read 0) */
-            const double up_as = __shfl_up(l_as, 1), up_aa = __shfl_up(l_aa, 1);
-            const double p_as = lane == 0 ? a_si : up_as, p_aa = lane == 0 ? a_ai : up_aa;
-            if (l_zero) {
-                l_dts = 0.5 * p_as * P.d_tau_k * dl;
-                l_dta = 0.5 * p_aa * P.d_tau_k * dl;
-                l_b0 = 0.0;
-            } else {
-                l_dts = 0.5 * (p_as + l_as) * P.d_tau_k * dl;
-                l_dta = 0.5 * (p_aa + l_aa) * P.d_tau_k * dl;
-                /* bias_func up to its weight cap (same operations) */
-                l_b0 = fdiv(100.0 * F.theta_e * F.theta_e, bias_d);
-                if (l_b0 < TP_OVER_TE) l_b0 = TP_OVER_TE;
-            }
-            const double d_tau = l_dta + l_dts;
-            l_fac = d_tau < 1.0e-3 ? (1.0 - d_tau * (1.0 / 24.0) * (24.0 - d_tau * (12.0 - d_tau * (4.0 - d_tau))))
-                                   : fexp(-d_tau);
-        }
-#ifdef GRM_TIMING
-        const unsigned long long tb1 = __builtin_amdgcn_s_memtime();
-        ti[0] += 1;
-        ti[1] += (unsigned long long)nb;
-        ti[2] += tb1 - tb0;
-#endif
-        /* The batch's leading run of PLAIN steps is committed at once: a step that interacts,
-         * neither stops, roulettes, scatters nor is absorbed changes the state only by w *= fac,
-         * tau += d_tau, one draw and the coefficients it leaves -- every lane decides its step from
-         * the weight before it (the sequential product, in the serial order, so bit-identical) and
-         * the draw at its counter; the first lane that is not plain ends the run, and its step (and
-         * the rest of the batch) goes through the serial code below. */
-        int bj0 = 0;
-        {
-            /* weight and optical depths before step j (lane j), and after all nb steps (lane nb) */
-            double w_run = w, ta_run = tau_abs, ts_run = tau_scatt;
-            double w_j = w, ta_j = tau_abs, ts_j = tau_scatt;
-            for (int j = 0; j < nb; ++j) {
-                if (lane == j) {
-                    w_j = w_run;
-                    ta_j = ta_run;
-                    ts_j = ts_run;
-                }
-                w_run = w_run * bcast(l_fac, j);
-                ta_run = ta_run + bcast(l_dta, j);
-                ts_run = ts_run + bcast(l_dts, j);
-            }
-            if (lane == nb) {
-                w_j = w_run;
-                ta_j = ta_run;
-                ts_j = ts_run;
-            }
-            /* the window of draws must hold counters rng.ctr .. rng.ctr + nb - 1 */
-            if (rng.ctr - wbase + (uint32_t)nb > 64u) {
-                wbase = rng.ctr;
-                Rng g = rng;
-                g.ctr = wbase + (uint32_t)lane;
-                win = uniform(g);
-            }
-            const double u = __shfl(win, (int)(rng.ctr - wbase) + (lane < nb ? lane : 0));
-            /* the state before step j: lane j - 1's results, or the carried ones for j = 0 */
-            const double up_x1 = __shfl_up(l_x1, 1), up_ne = __shfl_up(l_ne, 1);
-            const double up_as = __shfl_up(l_as, 1), up_aa = __shfl_up(l_aa, 1);
-            const double x1_prev = lane == 0 ? x1 : up_x1;
-            const double ne_prev = lane == 0 ? fl_ne : up_ne, as_prev = lane == 0 ? a_si : up_as,
-                         aa_prev = lane == 0 ? a_ai : up_aa;
-            /* bias_func with the weight cap (:1391-1404) and the interaction's bias (:977) */
-            double bf = 0.0;
-            if (!l_zero) {
-                const double max = w_j * (0.5 / WEIGHT_MIN);
-                double b = l_b0;
-                if (b > max) b = max;
-                bf = b * (1.0 / TP_OVER_TE);
-            }
-            const double up_bf = __shfl_up(bf, 1);
-            const double bi_prev = lane == 0 ? bi : up_bf;
-            const double bias = l_zero ? 0.0 : 0.5 * (bi_prev + bf);
-            const double bdt = bias * l_dts;
-            const bool may = bdt > (1.0 - u) * (1.0 - 0x1p-40);
-            const double lx = may ? -flog(u) : 0.0;
-            bool scatter = may && bdt > lx;
-            if (scatter) scatter = fdiv(w_j, bias) > WEIGHT_MIN;
-            const bool plain = lane < nb && !(x1_prev < P.x1_min) && !(x1_prev > P.x1_max) && !(w_j < WEIGHT_MIN) &&
-                               !(l_x1 < P.x1_min) && !(l_x1 > P.x1_max) && !isnan(l_x1) &&
-                               (aa_prev > 0.0 || as_prev > 0.0 || ne_prev > 0.0) && !scatter && !(l_dta > 100) &&
-                               n_step + lane + 1 <= MAX_N_STEP;
-            const unsigned long long np = __ballot(!plain);
-            bj0 = np ? __ffsll((long long)np) - 1 : 64; /* lanes >= nb are not plain: bj0 <= nb */
-            if (bj0 > 0) {
-                const int l = bj0 - 1;
-                w = bcast(w_j, bj0);
-                tau_abs = bcast(ta_j, bj0);
-                tau_scatt = bcast(ts_j, bj0);
-                x1 = bcast(l_x1, l);
-                fl_ne = bcast(l_ne, l);
-                a_si = bcast(l_as, l);
-                a_ai = bcast(l_aa, l);
-                bi = bcast(bf, l);
-                rng.ctr += (uint32_t)bj0;
-                n_step += bj0;
-                steps += (unsigned long long)bj0;
-                since += (unsigned)bj0;
-                cur = base + (unsigned long long)l;
-                si = base + (unsigned long long)bj0;
-                if (own) __hip_atomic_store(&pr.ctl.cons, si, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_WORKGROUP);
-            }
-        }
-        for (int bj = bj0; bj < nb; ++bj) {
-            ++since;
-            /* while (!stop_criterion(photon)) (:919) */
-            if (lone_stop(P, x1, w, rng, win, wbase, lane)) {
-                ended = done = true;
-                break;
-            }
-            /* photon_2, step size and push of this step: from the geometry wave */
-            cur = base + bj;
-            x1 = bcast(l_x1, bj);
-            ++steps;
-            if (lone_stop(P, x1, w, rng, win, wbase, lane)) { /* :932-934 */
-                ended = done = true;
-                break;
-            }
-            if (isnan(x1)) { /* a NaN position is absorbing (see transport_trip) */
-                if (own) atomicAdd(&C.ctr->n_nan, 1ull);
-                ended = done = true;
-                reason = 3;
-                break;
-            }
-            if (a_ai > 0.0 || a_si > 0.0 || fl_ne > 0.0) { /* :937 */
-                const bool zero = __builtin_amdgcn_readlane(l_zero, bj) != 0;
-                fl_ne = bcast(l_ne, bj);
-                double d_tau_scatt = bcast(l_dts, bj), d_tau_abs = bcast(l_dta, bj), bf = 0.0, bias = 0.0;
-                if (!zero) { /* bias_func's weight cap (:1391-1404) */
-                    const double max = w * (0.5 / WEIGHT_MIN);
-                    double b = bcast(l_b0, bj);
-                    if (b > max) b = max;
-                    bf = b * (1.0 / TP_OVER_TE);
-                    bias = 0.5 * (bi + bf);
-                }
-                a_si = bcast(l_as, bj);
-                a_ai = bcast(l_aa, bj);
-                bi = bf;
-                /* x1 = -log u, settled without the logarithm when possible (as in transport_trip) */
-                const double u = lone_draw(rng, win, wbase, lane);
-                const double bdt = bias * d_tau_scatt;
-                const bool may = bdt > (1.0 - u) * (1.0 - 0x1p-40);
-                const double lx = may ? -flog(u) : 0.0;
-                bool scatter = may && bdt > lx;
-                double wc = 0.0;
-                if (scatter) { /* w / bias only when it decides (:985) */
-                    wc = fdiv(w, bias);
-                    scatter = wc > WEIGHT_MIN;
-                }
-                if (scatter) { /* :985 */
-                    const double frac = fdiv(lx, bias * d_tau_scatt);
-                    d_tau_abs *= frac;
-                    if (d_tau_abs > 100) { /* absorbed before scattering */
-                        ended = done = true;
-                        reason = 2;
-                        break;
-                    }
-                    d_tau_scatt *= frac;
-                    const double d_tau = d_tau_abs + d_tau_scatt;
-                    if (d_tau_abs < 1.0e-3)
-                        w *= (1.0 - d_tau * (1.0 / 24.0) * (24.0 - d_tau * (12.0 - d_tau * (4.0 - d_tau))));
-                    else
-                        w *= fexp(-d_tau);
-                    /* photon_2 pushed to the scattering point (:1005-1010), by this wave */
-                    double x[4], k[4], dk[4], e_0_s;
-                    /* photon_2 of this step: the state after the step before, or the restart state */
-                    unpack13(base + bj == gen_start ? pr.ctl.rs : pr.ring[(base + bj - 1) % LONE_RING].out, x, k, dk,
-                             e_0_s);
-                    walk_push(P, x, k, dk, e_0_s, pr.ring[(base + bj) % LONE_RING].dl * frac, 0, 0u, rank, 0);
-                    Trig T;
-                    Gcov G;
-                    ZoneFetch Z;
-                    zone_fetch(P, x, Z);
-                    trig_at(P, x, T);
-                    gcov_from_trig(P, T, G);
-                    Fluid F;
-                    fluid_from(P, x, G, Z, F);
-                    fl_ne = F.n_e;
-                    x1 = x[1];
-                    cur = LONE_STOP; /* the state is the restart state from here on */
-                    if (F.n_e > 0.0 && (k[0] > 1.0e5 || k[0] < 0.0 || isnan(k[0]) || isnan(k[1]) || isnan(k[3]))) {
-                        /* scatter_super_photon's parent-side check (:1076-1081, :1018-1021) */
-                        k[0] = fabs(k[0]);
-                        w = 0.0;
-                        if (own) pack13(pr.ctl.rs, x, k, dk, e_0_s);
-                        ended = done = true;
-                        reason = 2;
-                        break;
-                    }
-                    const double nu2 = fluid_nu(k, F);
-                    double a_s2 = 0.0, a_a2 = 0.0;
-                    if (!(nu2 < 0.0)) radiation_coeffs(P, k, F, nu2, a_s2, a_a2);
-                    const double bf2 = bias_func(bias_d, F.theta_e, w);
-                    if (F.n_e > 0.0) {
-                        /* the child (:1015-1024): on the early worker into its queue, tracked by the
-                         * next free pair; else to the overflow pool, tracked by the relaunch */
-                        if (own) {
-                            if (kids)
-                                queue_child_push(C, kids, x, k, rng, n_scatt, cold, F, wc);
-                            else
-                                push_overflow(C, x, k, rng, n_scatt, cold, F, wc);
-                        }
-                        ++children;
-                    }
-                    a_si = a_s2;
-                    a_ai = a_a2;
-                    bi = bf2;
-                    /* the photon goes on from the scattering point: restart the geometry wave there */
-                    ++gen;
-                    gen_start = base + bj + 1;
-                    if (own) {
-                        pack13(pr.ctl.rs, x, k, dk, e_0_s);
-                        __hip_atomic_store(&pr.ctl.req, ((unsigned long long)gen << 32) | (base + bj + 1),
-                                           __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_WORKGROUP);
-                    }
-                    /* the end of the step here, and the end of the batch (the rest of it is on the old
-                     * geodesic): the batch's lane values are dead on this path */
-                    tau_abs += d_tau_abs;
-                    tau_scatt += d_tau_scatt;
-                    ++n_step; /* :1058-1063 */
-                    if (n_step > MAX_N_STEP) {
-                        ended = done = true;
-                        reason = 3;
-                        break;
-                    }
-                    si = base + bj + 1;
-                    if (own) __hip_atomic_store(&pr.ctl.cons, si, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_WORKGROUP);
-                    break;
-                } else {
-                    if (d_tau_abs > 100) { /* absorbed */
-                        ended = done = true;
-                        reason = 2;
-                        break;
-                    }
-                    w *= bcast(l_fac, bj);
-                }
-                tau_abs += d_tau_abs;
-                tau_scatt += d_tau_scatt;
-            }
-            ++n_step; /* :1058-1063 */
-            if (n_step > MAX_N_STEP) {
-                ended = done = true;
-                reason = 3;
-                break;
-            }
-            si = base + bj + 1;
-            if (own) __hip_atomic_store(&pr.ctl.cons, si, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_WORKGROUP);
-        }
-#ifdef GRM_TIMING
-        ti[3] += __builtin_amdgcn_s_memtime() - tb1;
-#endif
-    }
-#ifdef GRM_TIMING
-    /* slots 36-39: photons of > 1e5 steps, 40-43: the others */
-    if (own)
-        for (int r = 0; r < 4; ++r) atomicAdd(C.timing + (steps > 100000 ? 36 : 40) + r, ti[r]);
-#endif
-    gen_io = gen;
-    if (own) {
-        /* the photon's state: the end of step cur (its ring slot is not overwritten before this wave
-         * consumes the step after it), or the restart state */
-        double x[4], k[4], dk[4], e_0_s;
-        unpack13(cur == LONE_STOP ? pr.ctl.rs : pr.ring[cur % LONE_RING].out, x, k, dk, e_0_s);
-        if (abandoned) {
-            const unsigned long long slot = atomicAdd(C.stuck_count, 1ull);
-            if (slot < C.stuck_cap) {
-                double *r = C.stuck + slot * STUCK_WORDS;
-                r[0] = (double)rng.id;
-                r[1] = n_step;
-                r[2] = r[3] = r[4] = r[7] = 0.0;
-                r[5] = w;
-                r[6] = e_0_s;
-                for (int i = 0; i < 4; ++i) {
-                    r[8 + i] = x[i];
-                    r[12 + i] = k[i];
-                }
-            }
-            atomicAdd(&C.ctr->n_abandoned, 1ull);
-        } else if (ended) {
-            /* record_criterion (:1066) when the stop criterion ended it, else the reason's trace */
-            if (reason < 0 && x[1] > P.x1_max && n_step <= MAX_N_STEP)
-                record_photon(P, C, cold, rng.id, w, x[1], x[2], x[3], tau_abs, tau_scatt, n_scatt, n_step,
-                              reinterpret_cast<double *>(C.spec), (int)(sizeof(grm_spectrum_cell) / sizeof(double)));
-            else if (C.trace)
-                write_trace(C, cold, rng.id, w, x[1], x[2], x[3], tau_abs, tau_scatt, n_scatt, n_step,
-                            reason < 0 ? 2 : reason, -1, -1);
-        }
-        flush_counters(C);
-        atomicAdd(&C.ctr->n_steps, steps);
-        if (children) atomicAdd(&C.ctr->n_children, children);
-        atomicMax(&C.ctr->max_nstep, (unsigned long long)n_step);
-        if (n_step > 100000) atomicAdd(&C.ctr->n_long, 1ull);
-    }
-}
-
-#ifdef GRM_LONE_TU
-__device__ __forceinline__ bool child_setup_body(const Params &P, const Ctl &C, LoneRec *r, int lane);
-
-constexpr unsigned long long LK_STANDBY = 4; /* lone pairs that wait for children once their photon has ended */
-#ifndef GRM_LK_SLEEP
-#define GRM_LK_SLEEP 32
-#endif
-
-/* A lone pair after its own photon (GRM_OPT_EARLY_CHILDREN): the children the kernel's photons append
- * to lk_q, taken in order by whichever pair looks first, for as long as any pair still tracks a
- * photon (*lk_active), so that a long photon's child starts at once instead of in the relaunch after
- * the kernel.  A pair that finds the queue empty waits, up to LK_STANDBY pairs, or leaves.  Leaving
- * is safe whenever the queue is empty: a child is only appended by a pair that is tracking, and
- * every pair looks at the queue again when its photon ends.  Whole wave, uniform control. */
-__device__ void lone_children(const Params &P, const Ctl &C, int lane, LonePair &pr, unsigned &gen,
-                              unsigned long long n_handed) {
-    bool standing = false;
-    const unsigned long long t0 = __builtin_amdgcn_s_memrealtime();
-    while (true) {
-        /* every handed-over photon finished (its pair may not have started yet when a pair looks) */
-        const bool orig_done =
-            __hip_atomic_load(C.lk_orig, __ATOMIC_ACQUIRE, __HIP_MEMORY_SCOPE_AGENT) >= n_handed;
-        const unsigned long long act = __hip_atomic_load(C.lk_active, __ATOMIC_ACQUIRE, __HIP_MEMORY_SCOPE_AGENT);
-        const unsigned long long taken = __hip_atomic_load(C.lk_taken, __ATOMIC_ACQUIRE, __HIP_MEMORY_SCOPE_AGENT);
-        unsigned long long tail = __hip_atomic_load(C.lk_tail, __ATOMIC_ACQUIRE, __HIP_MEMORY_SCOPE_AGENT);
-        if (tail > C.lk_cap) tail = C.lk_cap;
-        if (taken < tail) {
-            /* counted as tracking before the claim, so that no waiting pair leaves in between */
-            unsigned long long got = ~0ull;
-            if (lane == 0) {
-                atomicAdd(C.lk_active, 1ull);
-                unsigned long long want = taken;
-                if (__hip_atomic_compare_exchange_strong(C.lk_taken, &want, taken + 1, __ATOMIC_ACQ_REL,
-                                                         __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT))
-                    got = taken;
-                else
-                    atomicAdd(C.lk_active, ~0ull);
-            }
-            got = ((unsigned long long)(uint32_t)__builtin_amdgcn_readfirstlane((int)(uint32_t)(got >> 32)) << 32) |
-                  (uint32_t)__builtin_amdgcn_readfirstlane((int)(uint32_t)got);
-            if (got == ~0ull) continue;
-            if (standing && lane == 0) atomicAdd(C.lk_standby, ~0ull);
-            standing = false;
-            while (__hip_atomic_load(C.lk_ready + got, __ATOMIC_ACQUIRE, __HIP_MEMORY_SCOPE_AGENT) != C.lk_tag)
-                __builtin_amdgcn_s_sleep(1);
-            LoneRec *r = C.lk_q + got;
-            if (child_setup_body(P, C, r, lane)) lone_interact(P, C, *r, lane, pr, gen, 2);
-            if (lane == 0) __hip_atomic_fetch_add(C.lk_active, ~0ull, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_AGENT);
-            continue;
-        }
-        if (act == 0 && orig_done) break; /* nothing queued or tracked, nothing to come: no child can */
-        if (!standing) {
-            unsigned long long sb = 0;
-            if (lane == 0) sb = atomicAdd(C.lk_standby, 1ull);
-            sb = (unsigned long long)__builtin_amdgcn_readfirstlane((int)sb);
-            if (sb >= LK_STANDBY) {
-                if (lane == 0) atomicAdd(C.lk_standby, ~0ull);
-                return;
-            }
-            standing = true;
-        }
-        /* a guard, not a path: every tracked photon ends within its own watchdog */
-        if (__builtin_amdgcn_s_memrealtime() - t0 > 2 * (C.watchdog_ticks ? C.watchdog_ticks : 6000000000ull)) {
-            if (lane == 0) __hip_atomic_store(&C.ctr->abort, 1ull, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-            break;
-        }
-        __builtin_amdgcn_s_sleep(GRM_LK_SLEEP);
-    }
-    if (standing && lane == 0) atomicAdd(C.lk_standby, ~0ull);
-}
-
-/* launched on lone_cap workgroups; the launch before handed over *C.lone_count photons, one to each of
- * the first workgroups; with GRM_OPT_EARLY_CHILDREN the next LK_STANDBY workgroups (as the grid
- * allows) start as standby pairs for the children, so that a launch of few photons -- a relaunch's
- * long photon -- does not track its photons' children one after another on their own pairs */
-__global__ __launch_bounds__(128) void lone_kernel(Params P, Ctl C) {
-    unsigned long long n_handed = __hip_atomic_load(C.lone_count, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    if (n_handed > C.lone_cap) n_handed = C.lone_cap;
-    const bool extra = blockIdx.x >= n_handed;
-    if (blockIdx.x >= C.lone_cap || (extra && (!C.lk_on || n_handed == 0 || blockIdx.x >= n_handed + LK_STANDBY)))
-        return;
-    const int wave = (int)(threadIdx.x >> 6);
-    const int lane = (int)(threadIdx.x & 63);
-    LonePair &pr = s_pair[0];
-    if (threadIdx.x < 8) s_cnt[threadIdx.x >> 2][threadIdx.x & 3] = 0;
-    if (threadIdx.x < LONE_RING) pr.ring[threadIdx.x].tag = 0;
-    if (threadIdx.x == 0) {
-        pr.ctl.cons = 0;
-        pr.ctl.req = 0;
-    }
-    __syncthreads();
-    if (wave == 1) {
-        lone_geometry(P, C, lane, pr);
-        return;
-    }
-    unsigned gen = 0;
-    if (!extra) {
-        if (C.lk_on && lane == 0) atomicAdd(C.lk_active, 1ull);
-        lone_interact(P, C, C.lone[blockIdx.x], lane, pr, gen, C.lk_on ? 2 : 0);
-        if (C.lk_on && lane == 0) {
-            /* its children are queued before it counts as finished (release) */
-            __hip_atomic_fetch_add(C.lk_orig, 1ull, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_AGENT);
-            __hip_atomic_fetch_add(C.lk_active, ~0ull, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_AGENT);
-        }
-    }
-    if (C.lk_on) lone_children(P, C, lane, pr, gen, n_handed);
-    if (lane == 0) __hip_atomic_store(&pr.ctl.req, LONE_STOP, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_WORKGROUP);
-}
-
-/* Concurrent worker for long photons (one workgroup of LONE_PAIRS two-wave pairs on a second
- * stream, beside the bulk launch): once it runs (early_live), a lane-loop photon that reaches early_steps steps is
- * handed over at the top of a step into the early queue (slot claimed by early_tail, published by
- * early_ready[slot] = early_tag); each pair's interaction wave claims slots in order (early_head),
- * waits for them to be published and tracks them with its geometry wave.  It exits once the bulk
- * launch has ended (early_done, set by its last workgroup) and every claimed slot is done.  Without
- * it such a photon would advance one step per lane-loop trip (~7 us) until the bulk ends. */
-/* A child request in a queue slot r (queue_child_push) made a photon at the top of its first
- * step: scatter_super_photon's sampling and the set-up at the head of track_super_photon
- * (harm_model.cpp:1083-1215, 895-917) -- the lane loop's sample_child, init_photon and set-up trip,
- * with the same functions: dk/dlambda from the connection at x (its zero-length push), the fluid,
- * both coefficients and the bias at x -- written back into the slot as the LoneRec a hand-over would
- * be.  The whole wave, identical values in every lane; lane 0 writes.  false = an invalid child
- * (traced with reason 4, as in the lane loop). */
-/* Inlined.  Out of line (a call) the early kernel's serial chain ran 1.299-1.307 us/step against
- * 1.306-1.313 inlined (tools/gpu_kids_ab.sh), but the same call from lone_kernel handed lone_interact
- * records whose weight came out NaN (every child of the lone kernel's photons; profiles/
- * r06_early_children/lk_debug.log) while the inlined body is photon-by-photon exact in both kernels. */
-__device__ __forceinline__ bool child_setup_body(const Params &P, const Ctl &C, LoneRec *r, int lane) {
-    SReq R;
-    load_sreq(reinterpret_cast<const SReq *>(r), R);
-    Rng rng;
-    rng.k0 = C.key0;
-    rng.k1 = C.key1;
-    double x[4], k[4], w;
-    Cold c;
-    if (lane == 0) atomicAdd(&C.ctr->n_tracked, 1ull);
-    bool ok = sample_child_core(P, R, rng, x, k, w, &c);
-    ok = ok && !(isnan(x[0]) || isnan(x[1]) || isnan(x[2]) || isnan(x[3]) || isnan(k[0]) || isnan(k[1]) ||
-                 isnan(k[2]) || isnan(k[3]) || w == 0.0);
-    if (!ok) {
-        /* both of the lane loop's invalid-child traces carry these values (id, weight, x of the
-         * request, no steps) */
-        if (lane == 0 && C.trace)
-            write_trace(C, &c, R.id, R.w, R.x[1], R.x[2], R.x[3], 0.0, 0.0, R.n_scatt, 0, 4, -1, -1);
-        return false;
-    }
-    Trig T;
-    trig_at(P, x, T);
-    Gcov G;
-    gcov_from_trig(P, T, G);
-    double dk[4];
-    {
-        Conn Cn;
-        connection(P, T, Cn);
-#pragma unroll
-        for (int i = 0; i < 4; ++i) dk[i] = geo_rhs(Cn, i, k);
-    }
-    ZoneFetch Z;
-    zone_fetch(P, x, Z);
-    Fluid F;
-    fluid_from(P, x, G, Z, F);
-    const double nu = fluid_nu(k, F);
-    double a_s = 0.0, a_a = 0.0;
-    radiation_coeffs(P, k, F, nu, a_s, a_a); /* the set-up evaluates them whatever nu (transport_trip) */
-    const double bf = bias_func(bias_den(P, C), F.theta_e, w);
-    if (lane == 0) {
-#pragma unroll
-        for (int i = 0; i < 4; ++i) {
-            r->x[i] = x[i];
-            r->k[i] = k[i];
-            r->dk[i] = dk[i];
-        }
-        r->w = w;
-        r->e_0_s = c.e;
-        r->tau_abs = 0.0;
-        r->tau_scatt = 0.0;
-        r->a_si = a_s;
-        r->a_ai = a_a;
-        r->bi = bf;
-        r->fl_ne = F.n_e;
-        r->c = c;
-        r->id = rng.id;
-        r->ctr = rng.ctr;
-        r->n_step = 0;
-        r->n_scatt = R.n_scatt;
-        r->pad = 0;
-    }
-    __threadfence(); /* the wave reads the record back (lone_interact) */
-    return true;
-}
-
-/* the early worker's next queue slot for the calling interaction wave, or ~0 when none will come.
- * Out of line (it touches only global memory): the kernel's SGPR spills 344 -> 265 */
-__device__ __attribute__((noinline)) unsigned long long early_claim(const Ctl &C, unsigned long long rt_start) {
-    unsigned long long slot = 0;
-    if ((threadIdx.x & 63) == 0) slot = atomicAdd(C.early_head, 1ull);
-    slot = (unsigned long long)__builtin_amdgcn_readfirstlane((int)slot); /* < 2^31 */
-    unsigned long long t_done = 0; /* when this wave first saw the bulk launch ended */
-    while (true) {
-        if (slot < C.early_cap &&
-            __hip_atomic_load(C.early_ready + slot, __ATOMIC_ACQUIRE, __HIP_MEMORY_SCOPE_AGENT) == C.early_tag)
-            return slot;
-        if (__hip_atomic_load(C.early_done, __ATOMIC_ACQUIRE, __HIP_MEMORY_SCOPE_AGENT) != 0) {
-            /* the bulk launch has ended: every claimed hand-over is published, so a slot past the
-             * claims (or past the queue) will never come -- unless a pair still tracking a photon may
-             * append a child (queue_child_push).  Slots finish in any order, but while this slot is
-             * unpublished every later one is too, so *early_fin >= slot says that every slot before
-             * it is finished: nothing is left that could append.  *early_fin is read before the tail
-             * (a pair appends before it counts its slot finished), and a pair that leaves counts its
-             * own slot, so the pair holding the next one can leave in turn. */
-            if (slot >= C.early_cap) return ~0ull;
-            const unsigned long long fin =
-                C.early_kids_on ? __hip_atomic_load(C.early_fin, __ATOMIC_ACQUIRE, __HIP_MEMORY_SCOPE_AGENT) : 0;
-            const unsigned long long tail = __hip_atomic_load(C.early_tail, __ATOMIC_ACQUIRE, __HIP_MEMORY_SCOPE_AGENT);
-            if (slot >= tail && (!C.early_kids_on || fin >= slot)) {
-                if (C.early_kids_on && (threadIdx.x & 63) == 0)
-                    __hip_atomic_fetch_add(C.early_fin, 1ull, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_AGENT);
-                return ~0ull;
-            }
-            /* a guard, not a path: the other pair's photon ends within its own watchdog; a count
-             * that never arrives (a bug) fails the call instead of keeping the GPU */
-            const unsigned long long now = __builtin_amdgcn_s_memrealtime();
-            if (t_done == 0) t_done = now;
-            if (now - t_done > 2 * (C.watchdog_ticks ? C.watchdog_ticks : 6000000000ull)) {
-                if ((threadIdx.x & 63) == 0) __hip_atomic_store(&C.ctr->abort, 1ull, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-                return ~0ull;
-            }
-        }
-        if (__builtin_amdgcn_s_memrealtime() - rt_start > EARLY_ALONE_TICKS &&
-            __builtin_amdgcn_readfirstlane(
-                (int)__hip_atomic_load(C.bulk_live, __ATOMIC_SEQ_CST, __HIP_MEMORY_SCOPE_AGENT)) == 0) {
-            /* no bulk workgroup has started: the launches are serialised and this one runs first.
-             * Close the queue, then leave unless a bulk workgroup started meanwhile (then reopen
-             * it: a workgroup that read 1 after starting is seen here by the store-load order) */
-            if ((threadIdx.x & 63) == 0) __hip_atomic_store(C.early_live, 2ull, __ATOMIC_SEQ_CST, __HIP_MEMORY_SCOPE_AGENT);
-            if (__builtin_amdgcn_readfirstlane(
-                    (int)__hip_atomic_load(C.bulk_live, __ATOMIC_SEQ_CST, __HIP_MEMORY_SCOPE_AGENT)) == 0)
-                return ~0ull;
-            if ((threadIdx.x & 63) == 0) __hip_atomic_store(C.early_live, 1ull, __ATOMIC_SEQ_CST, __HIP_MEMORY_SCOPE_AGENT);
-        }
-        __builtin_amdgcn_s_sleep(64);
-    }
-}
-
-__global__ __launch_bounds__(64 * 2 * LONE_PAIRS) void early_kernel(Params P, Ctl C) {
-    const int wave = (int)(threadIdx.x >> 6);
-    const int lane = (int)(threadIdx.x & 63);
-    LonePair &pr = s_pair[wave >> 1];
-    if (threadIdx.x < 4 * 2 * LONE_PAIRS) s_cnt[threadIdx.x >> 2][threadIdx.x & 3] = 0;
-    if (lane < LONE_RING) pr.ring[lane].tag = 0;
-    if (lane == 0) {
-        pr.ctl.cons = 0;
-        pr.ctl.req = 0;
-    }
-    __syncthreads();
-    const unsigned long long rt_start = __builtin_amdgcn_s_memrealtime();
-    if (threadIdx.x == 0) __hip_atomic_store(C.early_live, 1ull, __ATOMIC_SEQ_CST, __HIP_MEMORY_SCOPE_AGENT);
-    if (wave & 1) {
-        /* one inlined copy per pair: the pair's LDS block at a constant address, as in lone_kernel
-         * (with the block indexed by the wave the geometry step compiled to ~20 more instructions and
-         * ran 1.39 us per step against the lone kernel's 1.29-1.31; now 1.32-1.37) */
-        if (wave == 1)
-            lone_geometry(P, C, lane, s_pair[0]);
-        else
-            lone_geometry(P, C, lane, s_pair[1]);
-        return;
-    }
-    unsigned gen = 0;
-    while (true) {
-        const unsigned long long slot = early_claim(C, rt_start);
-        if (slot == ~0ull) break;
-        LoneRec *r = C.early_q + slot;
-        /* a child request (pad = 1, wave-uniform) becomes a photon at the top of its first step */
-        const bool go = r->pad != 1 || child_setup_body(P, C, r, lane);
-        if (go) lone_interact(P, C, *r, lane, pr, gen, C.early_kids_on ? 1 : 0);
-        if (C.early_kids_on && lane == 0)
-            __hip_atomic_fetch_add(C.early_fin, 1ull, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_AGENT);
-    }
-    if (lane == 0) __hip_atomic_store(&pr.ctl.req, LONE_STOP, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_WORKGROUP);
-}
-
-#endif /* GRM_LONE_TU */
-
-#if !defined(GRM_LONE_TU) && !defined(GRM_SPLIT_TU)
 /* One trip of the lane state machine = at most ONE geodesic push attempt, then, if that attempt
  * completed a step, the rest of the while-loop body of track_super_photon
  * (harm_model.cpp:919-1063).  A lane that has to halve its step (push_photon's recursion,
@@ -2729,12 +780,10 @@ __global__ __launch_bounds__(256) void ctl_kernel(CtlOp op) {
         __threadfence_system();
     }
 }
-#endif /* !GRM_LONE_TU && !GRM_SPLIT_TU */
 
 } /* namespace */
 
-#if !defined(GRM_LONE_TU) && !defined(GRM_SPLIT_TU)
-/* lone_kernel / early_kernel live in grm_lone.hip (the same source, compiled without
+/* lone_kernel / early_kernel live in grm_lone.hip (a unit compiled without
  * -disable-machine-licm, see there); Params and Ctl cross as bytes */
 extern "C" hipError_t grm_lone_launch(int which, unsigned grid, hipStream_t s, const void *P, size_t p_size,
                                       const void *C, size_t c_size);
@@ -4273,4 +2322,3 @@ size_t grm_sizeof(int which) {
 const char *grm_version(void) { return "grmonty_amd 0.1.0 (gfx950)"; }
 
 } /* extern "C" */
-#endif /* !GRM_LONE_TU && !GRM_SPLIT_TU */

@@ -41,13 +41,13 @@
  * frozen-bias batch equals the oracle photon by photon as the lane loop does
  * (tests/test_gpu_transport.py[split]).
  */
-#define GRM_SPLIT_TU 1
 /* only the interaction waves record: four record buffers per workgroup, indexed by the wave's pair */
 #include <hip/hip_runtime.h>
+#include <cstring>
 __shared__ int s_recidx[8]; /* wave -> its pair (interaction waves) */
 #define GRM_REC_WAVES 4
 #define GRM_REC_WAVE(t) (s_recidx[(t) >> 6])
-#include "grm_engine.hip"
+#include "grm_transport.h"
 
 namespace {
 

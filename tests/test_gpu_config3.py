@@ -19,7 +19,7 @@ here every counter is u64):
   - the job's warm-up ended on every rank, within WARMUP_MS of its launch start (a job barrier that
     never opened would hold it to the 1 s stall guard -- ADVICE r04), and EVERY rank admitted in
     batches: the ranks emit first and launch together, and the launches meet at the job's
-    device-side start barrier (job_started, grm_engine.hip), so no rank's warm-up begins after the
+    device-side start barrier (job_started, grm_transport.h), so no rank's warm-up begins after the
     job's has ended (round 5 saw two of eight ranks log only the closing entry);
   - no rank's early-worker queue filled (at 1,500 steps a 1.8e8-photon shard handed over
     888-1,024 photons to a 1,024-slot queue);

@@ -5,7 +5,7 @@
    (:1066, record_super_photon :1291-1295), so ending it early is output-equivalent.
 2. The per-launch watchdog (GRM_OPT_WATCHDOG_MS) abandons a launch that runs too long, reports it as
    an error with the abandoned photons' state, and the engine stays usable afterwards.
-3. The kernel-argument guard of track_kernel (kargs_check, grm_engine.hip): the launch's arguments
+3. The kernel-argument guard of track_kernel (kargs_check, grm_transport.h): the launch's arguments
    are read in the loop through the kernarg segment laid out as struct KArgs; every wave compares
    that view with the by-value parameters at entry.  A normal call reports it clean; with the
    failure injected (GRM_OPT_KARG_TEST) the call fails with the reason, tracks nothing, and the

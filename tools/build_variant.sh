@@ -2,6 +2,7 @@
 # Build the working tree's kernels with extra engine flags as an A/B variant:
 #   [SCHED=none|max-ilp|...] VFLAGS="-DX=1" tools/build_variant.sh <name>  ->  cuda-grmonty_amd/ab/libgrmonty_amd_v<name>.so
 #   (VFLAGS containing -DGRM_WITH_SPLIT also builds csrc/grm_split.hip, the role-split bulk kernel)
+# VFLAGS reach the three units that compile csrc/grm_transport.h: grm_engine, grm_lone, grm_split.
 set -e
 R="$(cd "$(dirname "$0")/.." && pwd)"
 name=$1

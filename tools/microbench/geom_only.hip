@@ -2,9 +2,11 @@
  * consumer instead of the interaction wave: does the geometry wave's chain run at the single-wave
  * push rate (push_lat.hip), and what does a busy neighbour wave with a large code footprint cost it?
  * Build: hipcc --offload-arch=gfx950 -O3 -mllvm -disable-machine-licm -I../../cuda-grmonty_amd/csrc
- *        geom_only.hip -o geom_only -L/opt/rocm/lib -lrccl -L../../cuda-grmonty_amd -lgrmonty_amd
- *        (includes the engine translation unit; the library supplies emission / probe symbols) */
-#include "../../cuda-grmonty_amd/csrc/grm_engine.hip"
+ *        geom_only.hip -o geom_only
+ *        (includes the engine's device headers only; links against nothing of the library) */
+#include "../../cuda-grmonty_amd/csrc/grm_transport.h"
+#include "../../cuda-grmonty_amd/csrc/grm_lone_pipe.h"
+#include <cstdio>
 #include <cstdlib>
 
 namespace {
