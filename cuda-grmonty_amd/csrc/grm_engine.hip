@@ -40,6 +40,7 @@
 
 #include "grm_transport.h"
 #include "grm_cellsums.h"
+#include "grm_rebin.h"
 #include "grm_emit.h"
 
 namespace {
@@ -828,6 +829,17 @@ struct grm_engine {
      * the first accumulate */
     unsigned long long trace_consumed = 0;
     double *d_cellsums = nullptr;
+    /* the trace re-binned on a caller's grid (grm_engine_rebin_*): records [0, rebin_consumed) are in
+     * d_rebin, rebin_doubles doubles and then the out-of-grid word; d_rebin_keys: the key pass's
+     * scratch, one word per record of the trace buffer (allocated by the first accumulate) */
+    bool rebin_on = false;
+    grm_bin_grid rebin_grid{};
+    double *d_rebin = nullptr;
+    size_t rebin_doubles = 0;
+    unsigned long long rebin_consumed = 0;
+    uint32_t *d_rebin_keys = nullptr;
+    unsigned long long rebin_keys_cap = 0;
+    double rebin_ms[2] = {0.0, 0.0}; /* key pass, slice passes of the last accumulate */
     uint64_t seed = 123;
     int bias_mode = 0;
     uint64_t id_base = 0;
@@ -1395,6 +1407,8 @@ int trace_count(grm_engine *e, unsigned long long &cnt) {
 
 /* the cell-sum accumulator and its skipped-record word behind it */
 constexpr size_t CELLSUMS_BYTES = GRM_CELLSUMS_DOUBLES * sizeof(double) + sizeof(unsigned long long);
+/* a re-binning table of `doubles` doubles and its out-of-grid word */
+constexpr size_t rebin_bytes(size_t doubles) { return doubles * sizeof(double) + sizeof(unsigned long long); }
 
 int reset_counters(grm_engine *e) {
     CtlOp op{};
@@ -1541,6 +1555,8 @@ void grm_engine_destroy(grm_engine *e) {
     hipFree(e->d_batch);
     hipFree(e->d_trace);
     hipFree(e->d_cellsums);
+    hipFree(e->d_rebin);
+    hipFree(e->d_rebin_keys);
     hipFree(e->d_upload);
     hipFree(e->d_timing);
     hipFree(e->d_waves);
@@ -1580,6 +1596,7 @@ int grm_engine_set_option(grm_engine *e, int opt, int64_t v) {
     case GRM_OPT_TRACE_CAP:
         /* the records counted so far are those of the old buffer (or of none): never binned */
         if (trace_count(e, e->trace_consumed)) return -1;
+        e->rebin_consumed = e->trace_consumed;
         if (e->d_trace) hipFree(e->d_trace);
         e->d_trace = nullptr;
         e->trace_cap = 0;
@@ -1679,6 +1696,8 @@ int grm_engine_reset(grm_engine *e) {
     e->history = 0;
     e->trace_consumed = 0; /* reset_counters zeroes the trace count */
     if (e->d_cellsums) HIPCHK(e, hipMemsetAsync(e->d_cellsums, 0, CELLSUMS_BYTES, e->stream));
+    e->rebin_consumed = 0;
+    if (e->d_rebin) HIPCHK(e, hipMemsetAsync(e->d_rebin, 0, rebin_bytes(e->rebin_doubles), e->stream));
     return reset_counters(e);
 }
 
@@ -1767,9 +1786,16 @@ int grm_engine_trace_rewind(grm_engine *e) {
     HIPCHK(e, hipSetDevice(e->device));
     unsigned long long cnt = 0;
     if (trace_count(e, cnt)) return -1;
-    if (e->trace_cap && cnt > e->trace_consumed) {
+    /* with a re-binning set up, the cell sums are a consumer only once they have been accumulated:
+     * a run that re-bins alone need not feed them.  With none, exactly as before. */
+    if (e->trace_cap && cnt > e->trace_consumed && (!e->rebin_on || e->d_cellsums)) {
         e->err = "trace rewind: " + std::to_string(cnt - e->trace_consumed) +
                  " records are not consumed yet (grm_engine_cell_sums_accumulate); a rewind would drop them";
+        return -1;
+    }
+    if (e->trace_cap && e->rebin_on && cnt > e->rebin_consumed) {
+        e->err = "trace rewind: " + std::to_string(cnt - e->rebin_consumed) +
+                 " records are not consumed yet by the rebin (grm_engine_rebin_accumulate); a rewind would drop them";
         return -1;
     }
     CtlOp op{};
@@ -1777,6 +1803,185 @@ int grm_engine_trace_rewind(grm_engine *e) {
     op.val[3] = 0;
     if (ctl(e, op, true)) return -1;
     e->trace_consumed = 0;
+    e->rebin_consumed = 0;
+    return 0;
+}
+
+/* --- the trace re-binned on a caller's grid (csrc/grm_rebin.hip) --- */
+int grm_engine_rebin_setup(grm_engine *e, const grm_bin_grid *grid) {
+    if (!e) return -1;
+    HIPCHK(e, hipSetDevice(e->device));
+    if (!grid) { /* release */
+        if (e->d_rebin) HIPCHK(e, hipFree(e->d_rebin));
+        e->d_rebin = nullptr;
+        e->rebin_doubles = 0;
+        e->rebin_on = false;
+        e->rebin_consumed = 0;
+        return 0;
+    }
+    if (const char *bad = grm_bin_grid_check(grid)) {
+        e->err = std::string("rebin setup: ") + bad;
+        return -1;
+    }
+    const size_t doubles = grm_bin_grid_doubles(grid);
+    if (doubles != e->rebin_doubles) {
+        double *d = nullptr;
+        HIPCHK(e, hipMalloc(&d, rebin_bytes(doubles))); /* a failure leaves the old table in force */
+        if (e->d_rebin) (void)hipFree(e->d_rebin);
+        e->d_rebin = d;
+        e->rebin_doubles = doubles;
+    }
+    e->rebin_grid = *grid;
+    e->rebin_grid.pad_ = 0;
+    e->rebin_on = true;
+    e->rebin_consumed = 0;
+    HIPCHK(e, hipMemsetAsync(e->d_rebin, 0, rebin_bytes(doubles), e->stream));
+    HIPCHK(e, hipStreamSynchronize(e->stream));
+    return 0;
+}
+
+int grm_engine_rebin_accumulate(grm_engine *e, uint64_t *n_binned, double *ms) {
+    if (!e) return -1;
+    if (n_binned) *n_binned = 0;
+    if (ms) *ms = 0.0;
+    HIPCHK(e, hipSetDevice(e->device));
+    if (!e->rebin_on) {
+        e->err = "rebin: no grid set up (grm_engine_rebin_setup)";
+        return -1;
+    }
+    if (!e->trace_cap) {
+        e->err = "rebin: the trace is off (GRM_OPT_TRACE_CAP)";
+        return -1;
+    }
+    unsigned long long cnt = 0;
+    if (trace_count(e, cnt)) return -1;
+    if (cnt > e->trace_cap) {
+        e->err = "rebin: the trace counted " + std::to_string(cnt) + " records but holds " +
+                 std::to_string(e->trace_cap) + " (GRM_OPT_TRACE_CAP): records were lost, nothing binned";
+        return -1;
+    }
+    if (e->rebin_keys_cap < e->trace_cap) {
+        if (e->d_rebin_keys) (void)hipFree(e->d_rebin_keys);
+        e->d_rebin_keys = nullptr;
+        e->rebin_keys_cap = 0;
+        HIPCHK(e, hipMalloc(&e->d_rebin_keys, (size_t)e->trace_cap * sizeof(uint32_t)));
+        e->rebin_keys_cap = e->trace_cap;
+    }
+    const unsigned long long c0 = std::min(e->rebin_consumed, cnt);
+    double t[2] = {0.0, 0.0};
+    if (grm_rebin_launch(grm_rebin_make(e->rebin_grid, e->P.xs2, e->P.xe2), e->d_trace + c0, (size_t)(cnt - c0),
+                         e->d_rebin_keys, e->d_rebin,
+                         reinterpret_cast<unsigned long long *>(e->d_rebin + e->rebin_doubles), e->stream, e->ev0,
+                         e->ev1, e->ev2, t, e->err))
+        return -1;
+    e->rebin_consumed = cnt;
+    e->rebin_ms[0] = t[0];
+    e->rebin_ms[1] = t[1];
+    if (n_binned) *n_binned = cnt - c0;
+    if (ms) *ms = t[0] + t[1];
+    return 0;
+}
+
+int grm_engine_rebin_read(grm_engine *e, double *out, size_t out_doubles, uint64_t *n_out_of_grid) {
+    if (!e) return -1;
+    HIPCHK(e, hipSetDevice(e->device));
+    if (!e->rebin_on) {
+        e->err = "rebin: no grid set up (grm_engine_rebin_setup)";
+        return -1;
+    }
+    if (!out || out_doubles != e->rebin_doubles) {
+        e->err = "rebin read: the grid in force has " + std::to_string(e->rebin_doubles) + " doubles, the caller gave " +
+                 std::to_string(out ? out_doubles : 0);
+        return -1;
+    }
+    unsigned long long og = 0;
+    HIPCHK(e, hipMemcpyAsync(out, e->d_rebin, e->rebin_doubles * sizeof(double), hipMemcpyDeviceToHost, e->stream));
+    HIPCHK(e, hipMemcpyAsync(&og, e->d_rebin + e->rebin_doubles, sizeof(og), hipMemcpyDeviceToHost, e->stream));
+    HIPCHK(e, hipStreamSynchronize(e->stream));
+    if (n_out_of_grid) *n_out_of_grid = og;
+    return 0;
+}
+
+int grm_engine_rebin_reset(grm_engine *e) {
+    if (!e) return -1;
+    HIPCHK(e, hipSetDevice(e->device));
+    if (e->d_rebin) {
+        HIPCHK(e, hipMemsetAsync(e->d_rebin, 0, rebin_bytes(e->rebin_doubles), e->stream));
+        HIPCHK(e, hipStreamSynchronize(e->stream));
+    }
+    return 0;
+}
+
+int grm_engine_rebin_grid(grm_engine *e, grm_bin_grid *out) {
+    if (!e || !out) return -1;
+    if (!e->rebin_on) {
+        e->err = "rebin: no grid set up (grm_engine_rebin_setup)";
+        return -1;
+    }
+    *out = e->rebin_grid;
+    return 0;
+}
+
+void *grm_engine_rebin_device_ptr(grm_engine *e) { return e ? (void *)e->d_rebin : nullptr; }
+
+int grm_engine_debug_rebin_ms(grm_engine *e, double out[2]) {
+    if (!e || !out) return -1;
+    out[0] = e->rebin_ms[0];
+    out[1] = e->rebin_ms[1];
+    return 0;
+}
+
+int grm_rebin_slice_cells(void) { return GRM_REBIN_SLICE_CELLS; }
+
+int grm_rebin_max_slices(void) { return grm_rebin_direct_slices(); }
+
+int grm_probe_rebin(grm_engine *e, const grm_bin_grid *grid, const grm_trace *host_records, size_t n, double *out,
+                    size_t out_doubles, uint64_t *n_out_of_grid) {
+    if (!e) return -1;
+    if (!grid || !out || (!host_records && n)) {
+        e->err = "grm_probe_rebin: null argument";
+        return -1;
+    }
+    if (const char *bad = grm_bin_grid_check(grid)) {
+        e->err = std::string("grm_probe_rebin: ") + bad;
+        return -1;
+    }
+    const size_t doubles = grm_bin_grid_doubles(grid);
+    if (out_doubles != doubles) {
+        e->err = "grm_probe_rebin: the grid has " + std::to_string(doubles) + " doubles, the caller gave " +
+                 std::to_string(out_doubles);
+        return -1;
+    }
+    HIPCHK(e, hipSetDevice(e->device));
+    grm_trace *d_rec = nullptr;
+    uint32_t *d_keys = nullptr;
+    double *d_acc = nullptr;
+    unsigned long long og = 0;
+    int rc = 0;
+    hipError_t st = hipMalloc(&d_acc, rebin_bytes(doubles));
+    if (st == hipSuccess && n) st = hipMalloc(&d_rec, n * sizeof(grm_trace));
+    if (st == hipSuccess && n) st = hipMalloc(&d_keys, n * sizeof(uint32_t));
+    if (st == hipSuccess) st = hipMemsetAsync(d_acc, 0, rebin_bytes(doubles), e->stream);
+    if (st == hipSuccess && n)
+        st = hipMemcpyAsync(d_rec, host_records, n * sizeof(grm_trace), hipMemcpyHostToDevice, e->stream);
+    if (st == hipSuccess)
+        rc = grm_rebin_launch(grm_rebin_make(*grid, e->P.xs2, e->P.xe2), d_rec, n, d_keys, d_acc,
+                              reinterpret_cast<unsigned long long *>(d_acc + doubles), e->stream, e->ev0, e->ev1, e->ev2,
+                              nullptr, e->err);
+    if (st == hipSuccess && rc == 0)
+        st = hipMemcpyAsync(out, d_acc, doubles * sizeof(double), hipMemcpyDeviceToHost, e->stream);
+    if (st == hipSuccess && rc == 0)
+        st = hipMemcpyAsync(&og, d_acc + doubles, sizeof(og), hipMemcpyDeviceToHost, e->stream);
+    if (st == hipSuccess) st = hipStreamSynchronize(e->stream);
+    hipFree(d_rec);
+    hipFree(d_keys);
+    hipFree(d_acc);
+    if (st != hipSuccess) {
+        e->err = std::string("grm_probe_rebin: ") + hipGetErrorString(st);
+        return -1;
+    }
+    if (rc) return -1;
+    if (n_out_of_grid) *n_out_of_grid = og;
     return 0;
 }
 
@@ -2315,6 +2520,7 @@ size_t grm_sizeof(int which) {
     case 4: return sizeof(grm_trace);
     case 5: return sizeof(grm_stats);
     case 6: return sizeof(grm_emit_zone);
+    case 7: return sizeof(grm_bin_grid);
     default: return 0;
     }
 }

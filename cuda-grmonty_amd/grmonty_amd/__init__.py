@@ -92,6 +92,50 @@ class Stats(C.Structure):
         return {k: getattr(self, k) for k, _ in self._fields_}
 
 
+class BinGrid(C.Structure):
+    """grm_bin_grid: the (theta, E) grid of Engine.rebin*.  BinGrid() is the engine's own grid;
+    BinGrid(n_th=18, n_e=400) divides the default energy range (200 bins of 0.25 in ln E from
+    1e-12) into n_e bins; log10_e=(lo, hi) gives another range, edge to edge in log10 E; l_e_0 (ln E
+    at the centre of bin 0) and d_l_e (bin width in ln E) set the two directly."""
+    _fields_ = [("n_th", C.c_int32), ("n_e", C.c_int32), ("fold", C.c_int32), ("pad_", C.c_int32),
+                ("l_e_0", C.c_double), ("d_l_e", C.c_double)]
+
+    def __init__(self, n_th: int = N_TH_BINS, n_e: int = N_E_BINS, fold: bool = True, l_e_0: float | None = None,
+                 d_l_e: float | None = None, log10_e: tuple | None = None):
+        super().__init__()
+        lib().grm_bin_grid_default(C.byref(self))
+        span0, lo0 = self.d_l_e * self.n_e, self.l_e_0 - 0.5 * self.d_l_e   # the default range, edge to edge
+        self.n_th, self.n_e, self.fold = int(n_th), int(n_e), int(fold)
+        if log10_e is not None:
+            lo0, span0 = log10_e[0] * np.log(10.0), (log10_e[1] - log10_e[0]) * np.log(10.0)
+        if d_l_e is None and (n_e != N_E_BINS or log10_e is not None) and n_e >= 1:
+            d_l_e = span0 / n_e
+            if l_e_0 is None:
+                l_e_0 = lo0 + 0.5 * d_l_e
+        if d_l_e is not None:
+            self.d_l_e = float(d_l_e)
+        if l_e_0 is not None:
+            self.l_e_0 = float(l_e_0)
+
+    @property
+    def rows(self) -> int:
+        return self.n_th if self.fold else 2 * self.n_th
+
+    @property
+    def shape(self) -> tuple:
+        return (N_ORDERS, self.rows, self.n_e, N_CELL_SUMS)
+
+    def check(self):
+        bad = lib().grm_bin_grid_check(C.byref(self))
+        if bad:
+            raise ValueError(bad.decode())
+        return self
+
+    def __repr__(self):
+        return (f"BinGrid(n_th={self.n_th}, n_e={self.n_e}, fold={self.fold}, l_e_0={self.l_e_0!r}, "
+                f"d_l_e={self.d_l_e!r})")
+
+
 # every entry point of include/grmonty_amd.h with its ctypes signature
 SIGNATURES = {
     "grm_engine_create": (C.c_int, [C.POINTER(Header), C.POINTER(DP), C.POINTER(Units), DP, DP, DP, C.c_int,
@@ -139,6 +183,20 @@ SIGNATURES = {
     "grm_engine_cell_sums_device_ptr": (VP, [VP]),
     "grm_probe_cell_sums": (C.c_int, [VP, VP, C.c_size_t, DP, C.POINTER(C.c_uint64)]),
     "grm_write_spectrum_orders": (C.c_int, [VP, DP, C.c_char_p]),
+    "grm_bin_grid_default": (None, [C.POINTER(BinGrid)]),
+    "grm_bin_grid_check": (C.c_char_p, [C.POINTER(BinGrid)]),
+    "grm_bin_grid_doubles": (C.c_size_t, [C.POINTER(BinGrid)]),
+    "grm_engine_rebin_setup": (C.c_int, [VP, C.POINTER(BinGrid)]),
+    "grm_engine_rebin_accumulate": (C.c_int, [VP, C.POINTER(C.c_uint64), DP]),
+    "grm_engine_rebin_read": (C.c_int, [VP, DP, C.c_size_t, C.POINTER(C.c_uint64)]),
+    "grm_engine_rebin_reset": (C.c_int, [VP]),
+    "grm_engine_rebin_grid": (C.c_int, [VP, C.POINTER(BinGrid)]),
+    "grm_engine_rebin_device_ptr": (VP, [VP]),
+    "grm_probe_rebin": (C.c_int, [VP, C.POINTER(BinGrid), VP, C.c_size_t, DP, C.c_size_t, C.POINTER(C.c_uint64)]),
+    "grm_rebin_slice_cells": (C.c_int, []),
+    "grm_rebin_max_slices": (C.c_int, []),
+    "grm_engine_debug_rebin_ms": (C.c_int, [VP, DP]),
+    "grm_write_spectrum_grid": (C.c_int, [VP, C.POINTER(BinGrid), DP, C.c_char_p]),
     "grm_rccl_unique_id": (C.c_int, [C.POINTER(C.c_uint8)]),
     "grm_engine_comm_init": (C.c_int, [VP, C.POINTER(C.c_uint8), C.c_int, C.c_int]),
     "grm_engine_allreduce": (C.c_int, [VP]),
@@ -315,6 +373,16 @@ class Model:
         if self.L.grm_write_spectrum_orders(self.h, a.ctypes.data_as(DP), path.encode()) != 0:
             raise IOError(self.L.grm_model_last_error().decode())
 
+    def write_spectrum_grid(self, grid: "BinGrid", sums: np.ndarray, path: str):
+        """write_spectrum_orders on a grid of the caller's, from Engine.rebin(): a '#' line naming the
+        grid, then n_e rows of log10(E) and, per theta row and order, nuLnu, sigma_nuLnu, n."""
+        a = np.ascontiguousarray(sums, dtype=np.float64)
+        want = self.L.grm_bin_grid_doubles(C.byref(grid))
+        if want and a.size != want:
+            raise ValueError(f"rebin sums: expected {grid.shape}, got {a.shape}")
+        if self.L.grm_write_spectrum_grid(self.h, C.byref(grid), a.ctypes.data_as(DP), path.encode()) != 0:
+            raise IOError(self.L.grm_model_last_error().decode())
+
 
 class Engine:
     """cuda_super_photon replacement: device buffers + persistent transport kernel on one GPU."""
@@ -433,6 +501,62 @@ class Engine:
         sk = C.c_uint64()
         self._check(self.L.grm_probe_cell_sums(self.h, _ptr(r), len(r), out.ctypes.data_as(DP), C.byref(sk)))
         return out, int(sk.value)
+
+    def rebin_setup(self, grid: "BinGrid | None" = None, **kw) -> "BinGrid":
+        """Set up the re-binning of the trace on `grid` (or BinGrid(**kw)): a zeroed accumulator,
+        and every record still in the trace buffer is binned by the next rebin_accumulate().
+        Raises for a grid outside the limits, leaving the engine as it was."""
+        g = grid if grid is not None else BinGrid(**kw)
+        self._check(self.L.grm_engine_rebin_setup(self.h, C.byref(g)))
+        return g
+
+    def rebin_release(self):
+        """drop the re-binning (trace_rewind then asks the cell sums alone again)"""
+        self._check(self.L.grm_engine_rebin_setup(self.h, None))
+
+    def rebin_grid(self) -> "BinGrid":
+        g = BinGrid()
+        self._check(self.L.grm_engine_rebin_grid(self.h, C.byref(g)))
+        return g
+
+    def rebin_accumulate(self) -> tuple[int, float]:
+        """Bin the trace records the re-binning has not seen yet, on the device; returns (records
+        walked, kernel ms).  Raises before rebin_setup and with the trace off or overflowed."""
+        n, ms = C.c_uint64(), C.c_double()
+        self._check(self.L.grm_engine_rebin_accumulate(self.h, C.byref(n), C.byref(ms)))
+        return int(n.value), float(ms.value)
+
+    def rebin_ms(self) -> tuple[float, float]:
+        """(key pass, slice passes) kernel ms of the last rebin_accumulate()"""
+        o = np.zeros(2)
+        self._check(self.L.grm_engine_debug_rebin_ms(self.h, o.ctypes.data_as(DP)))
+        return float(o[0]), float(o[1])
+
+    def rebin(self) -> tuple[np.ndarray, int]:
+        """(sums [N_ORDERS, rows, n_e, N_CELL_SUMS], n_out_of_grid) of the grid in force: the cell
+        sums' moments of every escaped superphoton (end_reason 0 and 1) that falls on the grid."""
+        g = self.rebin_grid()
+        out = np.zeros(g.shape)
+        og = C.c_uint64()
+        self._check(self.L.grm_engine_rebin_read(self.h, out.ctypes.data_as(DP), out.size, C.byref(og)))
+        return out, int(og.value)
+
+    def rebin_reset(self):
+        self._check(self.L.grm_engine_rebin_reset(self.h))
+
+    def rebin_device_ptr(self) -> int:
+        return int(self.L.grm_engine_rebin_device_ptr(self.h) or 0)
+
+    def probe_rebin(self, records: np.ndarray, grid: "BinGrid") -> tuple[np.ndarray, int]:
+        """the re-binning kernels on host trace records (scratch buffers; engine state stays as it
+        is): (sums, n_out_of_grid) as rebin()"""
+        r = np.ascontiguousarray(records, dtype=TRACE)
+        grid.check()
+        out = np.zeros(grid.shape)
+        og = C.c_uint64()
+        self._check(self.L.grm_probe_rebin(self.h, C.byref(grid), _ptr(r), len(r), out.ctypes.data_as(DP), out.size,
+                                           C.byref(og)))
+        return out, int(og.value)
 
     def upload(self, photons: np.ndarray) -> int:
         """Copy photons into an engine-owned device buffer; returns its device address."""

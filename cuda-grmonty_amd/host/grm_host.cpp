@@ -1036,6 +1036,73 @@ int grm_write_spectrum_orders(const grm_model *m, const double *sums, const char
     return ok ? 0 : set_err(std::string("write failed: ") + path);
 }
 
+void grm_bin_grid_default(grm_bin_grid *g) {
+    if (!g) return;
+    g->n_th = GRM_N_TH_BINS;
+    g->n_e = GRM_N_E_BINS;
+    g->fold = 1;
+    g->pad_ = 0;
+    g->l_e_0 = K.spec_l_e_0;
+    g->d_l_e = SPEC_D_L_E;
+}
+
+const char *grm_bin_grid_check(const grm_bin_grid *g) {
+    if (!g) return "null grid";
+    if (g->n_th < 1 || g->n_th > GRM_REBIN_MAX_TH) return "bin grid: n_th outside 1..GRM_REBIN_MAX_TH (512)";
+    if (g->n_e < 1 || g->n_e > GRM_REBIN_MAX_E) return "bin grid: n_e outside 1..GRM_REBIN_MAX_E (65536)";
+    if (g->fold != 0 && g->fold != 1) return "bin grid: fold is neither 0 nor 1";
+    if (!std::isfinite(g->l_e_0)) return "bin grid: l_e_0 is not finite";
+    if (!(g->d_l_e > 0.0) || !std::isfinite(g->d_l_e)) return "bin grid: d_l_e is not a finite width > 0";
+    if ((long long)(g->fold ? 1 : 2) * g->n_th * g->n_e > GRM_REBIN_MAX_CELLS)
+        return "bin grid: n_th and n_e give more than GRM_REBIN_MAX_CELLS (1048576) rows x n_e";
+    return nullptr;
+}
+
+size_t grm_bin_grid_doubles(const grm_bin_grid *g) {
+    if (grm_bin_grid_check(g)) return 0;
+    return (size_t)GRM_N_ORDERS * (size_t)(g->fold ? 1 : 2) * g->n_th * g->n_e * GRM_N_CELL_SUMS;
+}
+
+/* grm_write_spectrum_orders on a grid of the caller's: the same factor with d_l_e for SPEC_D_L_E.
+ * The coordinate map is symmetric about the equator, so a south row of an unfolded grid takes the
+ * solid angle of its mirror image: the two rows of a pair carry the same bits. */
+int grm_write_spectrum_grid(const grm_model *m, const grm_bin_grid *g, const double *sums, const char *path) {
+    if (!m || !g || !sums || !path) return set_err("null argument");
+    if (const char *bad = grm_bin_grid_check(g)) return set_err(std::string("write spectrum grid: ") + bad);
+    const grm_header &h = m->hdr;
+    const double dx2 = (h.x_stop[2] - h.x_start[2]) / (2 * g->n_th);
+    auto d_omega = [&](double a, double b) {
+        return 2.0 * kPi *
+               (-std::cos(kPi * b + 0.5 * (1.0 - h.h_slope) * std::sin(2 * kPi * b)) +
+                std::cos(kPi * a + 0.5 * (1.0 - h.h_slope) * std::sin(2 * kPi * a)));
+    };
+    const int rows = g->fold ? g->n_th : 2 * g->n_th;
+    FILE *fp = std::fopen(path, "w");
+    if (!fp) return set_err(std::string("Cannot open file ") + path);
+    std::fprintf(fp,
+                 "# grid n_th=%d n_e=%d fold=%d l_e_0=%.17g d_l_e=%.17g; log10(E/me c^2); per theta row 0..%d (%s) and "
+                 "scattering order 0, 1, 2, >=3: nuLnu sigma_nuLnu n "
+                 "(sigma: independent superphotons; parent-child correlation ignored)\n",
+                 g->n_th, g->n_e, g->fold, g->l_e_0, g->d_l_e, rows - 1,
+                 g->fold ? "north and south folded" : "north pole to south pole");
+    const size_t cells = (size_t)rows * g->n_e;
+    for (int i = 0; i < g->n_e; ++i) {
+        std::fprintf(fp, "%.17g", (i * g->d_l_e + g->l_e_0) / kLn10);
+        for (int r = 0; r < rows; ++r) {
+            const int j = r < g->n_th ? r : 2 * g->n_th - 1 - r; /* the row's, or its mirror image's, north interval */
+            const double dom = (g->fold ? 2.0 : 1.0) * d_omega(j * dx2, (j + 1) * dx2);
+            const double fac = (ME * CL * CL) * (4.0 * kPi / dom) * (1.0 / g->d_l_e);
+            for (int o = 0; o < GRM_N_ORDERS; ++o) {
+                const double *c = sums + ((size_t)o * cells + (size_t)r * g->n_e + i) * GRM_N_CELL_SUMS;
+                std::fprintf(fp, " %.17g %.17g %.17g", fac * c[3] / L_SUN, fac * std::sqrt(c[4]) / L_SUN, c[0]);
+            }
+        }
+        std::fprintf(fp, "\n");
+    }
+    const bool ok = std::fclose(fp) == 0;
+    return ok ? 0 : set_err(std::string("write failed: ") + path);
+}
+
 int grm_engine_create_from_model(const grm_model *m, int device, grm_engine **out) {
     if (!m || !m->inited) return set_err("model not initialised");
     const double *f[8];

@@ -6,6 +6,7 @@
  *               [--mass_unit=4e19] [--verbosity=info] [--device=0] [--seed=123]
  *               [--batch=67108864] [--threads=0] [--host_emit] [--stats_path=OUT.stats]
  *               [--orders_path=OUT.orders] [--trace_cap=N]
+ *               [--rebin=N_TH,N_E[,LOG10_E_MIN,LOG10_E_MAX][,unfold] --rebin_path=OUT.grid]
  *
  * read_file -> init -> run_simulation (zone batches emitted and tracked on the GPU; --host_emit:
  * emitted on host threads, batch b+1 overlapping the transport of batch b) -> report_spectrum.
@@ -13,9 +14,14 @@
  * the run then keeps the per-photon trace, bins it on the GPU after every zone batch
  * (grm_engine_cell_sums_accumulate) and rewinds it.  --trace_cap: trace records per batch (default:
  * TRACE_PER_PHOTON x the batch's emitted photons); a batch that needs more ends the run with an error.
+ * --rebin with --rebin_path: the same spectrum on a (theta, E) grid chosen here -- N_TH theta bins per
+ * hemisphere (folded about the equator, or with "unfold" 2 N_TH rows pole to pole) and N_E energy bins
+ * over the default range (1e-12 upward, 200 x 0.25 in ln E) or over [LOG10_E_MIN, LOG10_E_MAX] --
+ * re-binned on the GPU from the same trace (grm_engine_rebin_accumulate, grm_write_spectrum_grid).
  * "Final rate" = created superphotons / wall time of run_simulation, as in the reference.
  */
 #include <chrono>
+#include <cmath>
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
@@ -64,12 +70,51 @@ bool flag(int argc, char **argv, int &i, const char *name, std::string &val) {
  * many: such a run says how many records it needed and wants --trace_cap. */
 constexpr double TRACE_PER_PHOTON = 8.8;
 
+/* --rebin=N_TH,N_E[,LOG10_E_MIN,LOG10_E_MAX][,unfold]; false for a malformed list */
+bool parse_rebin(const std::string &v, grm_bin_grid &g) {
+    std::vector<std::string> f;
+    size_t a = 0;
+    for (;;) {
+        const size_t b = v.find(',', a);
+        f.push_back(v.substr(a, b == std::string::npos ? b : b - a));
+        if (b == std::string::npos) break;
+        a = b + 1;
+    }
+    grm_bin_grid_default(&g);
+    if (!f.empty() && f.back() == "unfold") {
+        g.fold = 0;
+        f.pop_back();
+    }
+    if (f.size() != 2 && f.size() != 4) return false;
+    double x[4] = {0.0, 0.0, 0.0, 0.0};
+    for (size_t i = 0; i < f.size(); ++i) {
+        char *end = nullptr;
+        x[i] = std::strtod(f[i].c_str(), &end);
+        if (f[i].empty() || *end || !std::isfinite(x[i])) return false;
+    }
+    if (x[0] < 1.0 || x[0] > 1e9 || x[0] != std::floor(x[0]) || x[1] < 1.0 || x[1] > 1e9 || x[1] != std::floor(x[1]))
+        return false;
+    /* the range edge to edge: the default grid's, or the one given; bin 0 is centred half a bin in */
+    double lo = g.l_e_0 - 0.5 * g.d_l_e, span = g.d_l_e * g.n_e;
+    if (f.size() == 4) {
+        if (!(x[3] > x[2])) return false;
+        const double ln10 = std::log(10.0);
+        lo = x[2] * ln10;
+        span = (x[3] - x[2]) * ln10;
+    }
+    g.n_th = (int32_t)x[0];
+    g.n_e = (int32_t)x[1];
+    g.d_l_e = span / g.n_e;
+    g.l_e_0 = lo + 0.5 * g.d_l_e;
+    return true;
+}
+
 } /* namespace */
 
 int main(int argc, char **argv) {
     long long photon_n = 5000000; /* main.cpp:20 */
     double mass_unit = 4e19;      /* main.cpp:21 */
-    std::string dump, spec_path, stats_path, orders_path, verbosity = "info";
+    std::string dump, spec_path, stats_path, orders_path, rebin_arg, rebin_path, verbosity = "info";
     int device = 0, threads = 0;
     unsigned long long seed = 123; /* consts.hpp:14 */
     long long batch = 1ll << 26; /* photons per zone batch (8.6 GB of emitted photons) */
@@ -84,6 +129,8 @@ int main(int argc, char **argv) {
         else if (flag(argc, argv, i, "verbosity", v)) verbosity = v;
         else if (flag(argc, argv, i, "stats_path", v)) stats_path = v;
         else if (flag(argc, argv, i, "orders_path", v)) orders_path = v;
+        else if (flag(argc, argv, i, "rebin_path", v)) rebin_path = v;
+        else if (flag(argc, argv, i, "rebin", v)) rebin_arg = v;
         else if (flag(argc, argv, i, "trace_cap", v)) trace_cap = std::atoll(v.c_str());
         else if (flag(argc, argv, i, "device", v)) device = std::atoi(v.c_str());
         else if (flag(argc, argv, i, "seed", v)) seed = std::strtoull(v.c_str(), nullptr, 10);
@@ -92,6 +139,19 @@ int main(int argc, char **argv) {
         else if (std::strcmp(argv[i], "--host_emit") == 0) host_emit = true;
         else {
             std::fprintf(stderr, "unknown argument %s\n", argv[i]);
+            return 2;
+        }
+    }
+    const bool rebin = !rebin_arg.empty() || !rebin_path.empty();
+    grm_bin_grid grid;
+    grm_bin_grid_default(&grid);
+    if (rebin) {
+        const char *bad = nullptr;
+        if (rebin_arg.empty() || rebin_path.empty()) bad = "--rebin and --rebin_path go together";
+        else if (!parse_rebin(rebin_arg, grid)) bad = "malformed --rebin list";
+        else bad = grm_bin_grid_check(&grid);
+        if (bad) {
+            std::fprintf(stderr, "%s\nusage: --rebin=N_TH,N_E[,LOG10_E_MIN,LOG10_E_MAX][,unfold] --rebin_path=FILE\n", bad);
             return 2;
         }
     }
@@ -153,8 +213,13 @@ int main(int argc, char **argv) {
         buf.resize((size_t)std::max<int64_t>(n, 0));
         if (n > 0) grm_model_emit(m, seed, cuts[b], cuts[b + 1], buf.data(), buf.size(), threads);
     };
-    /* --orders_path: size the trace for the batch about to be tracked, and bin + rewind it after */
+    /* --orders_path / --rebin: size the trace for the batch about to be tracked, and bin + rewind it after */
     const bool orders = !orders_path.empty();
+    const bool traced = orders || rebin;
+    if (rebin && grm_engine_rebin_setup(e, &grid)) {
+        std::fprintf(stderr, "[error] rebin: %s\n", grm_engine_last_error(e));
+        return 1;
+    }
     long long cap_now = 0;
     auto trace_for = [&](size_t n) {
         const long long want = trace_cap > 0 ? trace_cap : (long long)(TRACE_PER_PHOTON * (double)n) + 1024;
@@ -165,16 +230,23 @@ int main(int argc, char **argv) {
     auto bin_trace = [&]() {
         uint64_t nb = 0;
         double ms = 0.0;
-        if (grm_engine_cell_sums_accumulate(e, &nb, &ms) || grm_engine_trace_rewind(e)) return -1;
-        info("Binned %llu trace records by scattering order in %.3f ms", (unsigned long long)nb, ms);
-        return 0;
+        if (orders) {
+            if (grm_engine_cell_sums_accumulate(e, &nb, &ms)) return -1;
+            info("Binned %llu trace records by scattering order in %.3f ms", (unsigned long long)nb, ms);
+        }
+        if (rebin) {
+            if (grm_engine_rebin_accumulate(e, &nb, &ms)) return -1;
+            info("Re-binned %llu trace records on the %d x %d grid in %.3f ms", (unsigned long long)nb,
+                 grid.fold ? grid.n_th : 2 * grid.n_th, grid.n_e, ms);
+        }
+        return grm_engine_trace_rewind(e) ? -1 : 0;
     };
     if (host_emit) emit(0, cur);
     for (size_t b = 0; b + 1 < cuts.size(); ++b) {
         if (host_emit) {
             std::thread prod;
             if (b + 2 < cuts.size()) prod = std::thread(emit, b + 1, std::ref(nxt));
-            if (orders && !cur.empty() && trace_for(cur.size())) {
+            if (traced && !cur.empty() && trace_for(cur.size())) {
                 std::fprintf(stderr, "[error] trace: %s\n", grm_engine_last_error(e));
                 if (prod.joinable()) prod.join();
                 return 1;
@@ -191,15 +263,15 @@ int main(int argc, char **argv) {
         } else {
             grm_init_photon *d_ph = nullptr;
             uint64_t n = 0;
-            if (grm_engine_emit(e, seed, cuts[b], cuts[b + 1], &d_ph, &n) || (orders && n && trace_for(n)) ||
+            if (grm_engine_emit(e, seed, cuts[b], cuts[b + 1], &d_ph, &n) || (traced && n && trace_for(n)) ||
                 (n && grm_engine_track_device(e, d_ph, n))) {
                 std::fprintf(stderr, "[error] emission/transport: %s\n", grm_engine_last_error(e));
                 return 1;
             }
             created += n;
         }
-        if (orders && cap_now && bin_trace()) {
-            std::fprintf(stderr, "[error] cell sums: %s\n", grm_engine_last_error(e));
+        if (traced && cap_now && bin_trace()) {
+            std::fprintf(stderr, "[error] trace binning: %s\n", grm_engine_last_error(e));
             return 1;
         }
         const double el = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
@@ -250,6 +322,20 @@ int main(int argc, char **argv) {
                                   (unsigned long long)skipped);
         info("Writing spectrum by scattering order to file %s", orders_path.c_str());
         if (grm_write_spectrum_orders(m, sums.data(), orders_path.c_str())) {
+            std::fprintf(stderr, "[error] %s\n", grm_model_last_error());
+            return 1;
+        }
+    }
+    if (rebin) {
+        std::vector<double> sums(grm_bin_grid_doubles(&grid));
+        uint64_t out_of_grid = 0;
+        if (grm_engine_rebin_read(e, sums.data(), sums.size(), &out_of_grid)) {
+            std::fprintf(stderr, "[error] rebin: %s\n", grm_engine_last_error(e));
+            return 1;
+        }
+        if (out_of_grid) info("Rebin: %llu escaped superphotons fell outside the grid", (unsigned long long)out_of_grid);
+        info("Writing the re-binned spectrum to file %s", rebin_path.c_str());
+        if (grm_write_spectrum_grid(m, &grid, sums.data(), rebin_path.c_str())) {
             std::fprintf(stderr, "[error] %s\n", grm_model_last_error());
             return 1;
         }

@@ -269,6 +269,64 @@ int grm_engine_cell_sums_read(grm_engine *e, double *out, uint64_t *n_skipped);
 int grm_engine_cell_sums_reset(grm_engine *e);
 int grm_engine_trace_rewind(grm_engine *e);
 void *grm_engine_cell_sums_device_ptr(grm_engine *e);
+
+/* --- the trace re-binned on a caller-chosen theta / E grid (csrc/grm_rebin.hip) ----------- */
+/* The engine's own outputs sit on the reference's compile-time grid (GRM_N_TH_BINS folded theta
+ * bins, GRM_N_E_BINS energy bins of 0.25 in ln E from 1e-12).  The trace keeps every ended
+ * superphoton's x2 and e, so a second binning kernel places them on any grid, chosen per call;
+ * one traced run can be binned at several resolutions and the transport is untouched. */
+#define GRM_REBIN_MAX_TH 512           /* theta bins per hemisphere */
+#define GRM_REBIN_MAX_E 65536          /* energy bins */
+#define GRM_REBIN_MAX_CELLS (1 << 20)  /* rows x n_e: the accumulator is 160 B per cell, 168 MB at most */
+#define GRM_REBIN_SLICE_CELLS 1200     /* cells of one order a workgroup of the slice passes keeps in LDS (48 KB) */
+typedef struct grm_bin_grid {
+    int32_t n_th;   /* theta bins per hemisphere, 1..GRM_REBIN_MAX_TH */
+    int32_t n_e;    /* energy bins, 1..GRM_REBIN_MAX_E */
+    int32_t fold;   /* 1: north and south share a row (the reference); 0: 2*n_th rows, pole to pole */
+    int32_t pad_;
+    double l_e_0;   /* ln E at the centre of energy bin 0 */
+    double d_l_e;   /* bin width in ln E, > 0 and finite */
+} grm_bin_grid;
+/* the engine's own grid: {GRM_N_TH_BINS, GRM_N_E_BINS, 1, 0, log(1e-12), 0.25} */
+void grm_bin_grid_default(grm_bin_grid *g);
+/* null for a grid inside the limits (rows x n_e <= GRM_REBIN_MAX_CELLS too), else a message that
+ * names the offending field (a static string) */
+const char *grm_bin_grid_check(const grm_bin_grid *g);
+/* doubles of the grid's table, GRM_N_ORDERS x rows x n_e x GRM_N_CELL_SUMS with rows = n_th folded,
+ * 2 n_th unfolded; 0 for a grid grm_bin_grid_check refuses */
+size_t grm_bin_grid_doubles(const grm_bin_grid *g);
+/* The cell of a record comes from its x2 and e by record_super_photon's own expressions
+ * (harm_model.cpp:1291-1335), with dx2 = (x_stop[2] - x_start[2]) / (2 n_th):
+ *   north = x2 < (x_start[2] + x_stop[2]) / 2;  i = (int)(north ? x2 / dx2 : (x_stop[2] - x2) / dx2);
+ *   i_e = (int)((ln e - l_e_0) / d_l_e + 2.5) - 2;
+ * row = i folded; unfolded i for north and 2 n_th - 1 - i for south (north + mirrored south is the
+ * folded table).  Records of end_reason 0 and 1 -- every superphoton that escaped -- are considered,
+ * so a wider grid than the engine's picks up what the engine could not bin; a record whose w, e or
+ * x2 is NaN, whose row or energy bin is outside the grid or whose n_scatt is negative is *out of
+ * grid*: skipped and counted.  Table: sums[GRM_N_ORDERS][rows][n_e][GRM_N_CELL_SUMS], the cell sums'
+ * moments and order clamp.
+ *
+ * grm_engine_rebin_setup validates the grid (-1 and a message naming the field; engine state
+ * untouched), allocates the zeroed accumulator with one out-of-grid counter word behind it, and
+ * sets the re-binning's own consumed mark to 0: the records still in the trace buffer are binned
+ * (again) by the next accumulate.  A null grid releases the re-binning.
+ * grm_engine_rebin_accumulate bins the records [mark, count) and advances the mark (*n_binned = the
+ * records it walked, *ms = the time of its kernels, HIP events); it fails (-1,
+ * accumulator and mark untouched) before a setup, with the trace off and when the trace overflowed
+ * (the message gives count and capacity).  grm_engine_rebin_read copies the table out; out_doubles
+ * must be grm_bin_grid_doubles of the grid in force.  grm_engine_rebin_reset zeroes the accumulator;
+ * grm_engine_reset zeroes it and the mark; changing GRM_OPT_TRACE_CAP marks every record counted so
+ * far as consumed.  While a re-binning is set up, grm_engine_trace_rewind also refuses while IT
+ * holds unconsumed records, and asks the cell sums only once they have been accumulated at least
+ * once (a run that re-bins alone need not feed them).  grm_engine_rebin_grid: the grid in force
+ * (-1 before a setup).  grm_engine_rebin_device_ptr: the accumulator's device address (null before
+ * a setup), for an in-place collective. */
+int grm_engine_rebin_setup(grm_engine *e, const grm_bin_grid *grid);
+int grm_engine_rebin_accumulate(grm_engine *e, uint64_t *n_binned, double *ms);
+int grm_engine_rebin_read(grm_engine *e, double *out, size_t out_doubles, uint64_t *n_out_of_grid);
+int grm_engine_rebin_reset(grm_engine *e);
+int grm_engine_rebin_grid(grm_engine *e, grm_bin_grid *out);
+void *grm_engine_rebin_device_ptr(grm_engine *e);
 /* copy a host batch into an engine-owned device buffer once (inputs resident in HBM); *dev_out is
  * valid for grm_engine_track_device until the next upload or destroy. */
 int grm_engine_upload(grm_engine *e, const grm_init_photon *batch, size_t n, grm_init_photon **dev_out);
@@ -418,9 +476,18 @@ int grm_write_spectrum_stats(const grm_model *m, const grm_spectrum_cell *spectr
  * superphotons.  A scattered child is correlated with its parent (one family shares its history),
  * which this estimate ignores: it is a lower bound where scattering families dominate a cell. */
 int grm_write_spectrum_orders(const grm_model *m, const double *sums, const char *path);
+/* the same on a grid of the caller's (sums: grm_engine_rebin_read's table of that grid): a '#'
+ * header line naming the grid, then n_e rows of log10(E) and, per theta row and per order 0, 1, 2,
+ * >= 3, nuLnu, sigma_nuLnu and n, "%.17g" (1 + rows * 4 * 3 columns).  The factor is
+ * grm_write_spectrum_orders' with d_l_e for 0.25; the solid angle of a folded row is twice that of
+ * its x2 interval, of an unfolded row that of its own interval (a south row's is taken from its
+ * mirror image, so the two rows of a pair get the same bits).  sigma is the same
+ * independent-superphoton estimate.  With the default grid the file is grm_write_spectrum_orders'
+ * from its second line on. */
+int grm_write_spectrum_grid(const grm_model *m, const grm_bin_grid *grid, const double *sums, const char *path);
 
 /* ABI introspection: sizes of the POD structs (0 header 1 units 2 init_photon 3 spectrum_cell
- * 4 trace 5 stats 6 emit_zone) */
+ * 4 trace 5 stats 6 emit_zone 7 bin_grid) */
 size_t grm_sizeof(int which);
 const char *grm_version(void);
 

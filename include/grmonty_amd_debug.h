@@ -70,6 +70,20 @@ int grm_probe(grm_engine *e, int which, const double *in, int in_stride, double 
  * buffer, bins them into a scratch accumulator and returns it in out[GRM_N_ORDERS][cells]
  * [GRM_N_CELL_SUMS] and *n_skipped.  Touches neither the engine's trace nor its accumulator. */
 int grm_probe_cell_sums(grm_engine *e, const grm_trace *host_records, size_t n, double *out, uint64_t *n_skipped);
+/* the re-binning kernels (csrc/grm_rebin.hip) on n host trace records and the given grid, in scratch
+ * buffers: out[out_doubles] (grm_bin_grid_doubles of the grid, else an error) and *n_out_of_grid.
+ * Touches neither the engine's trace nor its re-binning. */
+int grm_probe_rebin(grm_engine *e, const grm_bin_grid *grid, const grm_trace *host_records, size_t n, double *out,
+                    size_t out_doubles, uint64_t *n_out_of_grid);
+/* cells of one order that a workgroup of the re-binning's slice pass keeps in LDS (tests place their
+ * grids around it) */
+int grm_rebin_slice_cells(void);
+/* a table of more slices than this, all orders together, takes the other accumulation path: direct
+ * global atomics instead of LDS slices (csrc/grm_rebin.hip) */
+int grm_rebin_max_slices(void);
+/* kernel times (ms, HIP events) of the last grm_engine_rebin_accumulate: out[0] the key pass,
+ * out[1] the accumulation (the slice passes, or the direct-atomics pass of a large table) */
+int grm_engine_debug_rebin_ms(grm_engine *e, double out[2]);
 
 #ifdef __cplusplus
 }

@@ -14,7 +14,7 @@ make -s -C "$R/cuda-grmonty_amd" build/grm_host.o
 FL="-O3 -std=c++17 -fPIC --offload-arch=gfx950 -Wno-unused-result -Wno-unused-value -mllvm -disable-machine-licm"
 SF=""; [ -n "$SCHED" ] && SF="-mllvm -amdgpu-sched-strategy=$SCHED"  # revisions before 58fc566 were built with SCHED=iterative-ilp
 objs=""; pids=""
-for u in grm_engine grm_lone grm_split grm_probe grm_emit grm_tables grm_cellsums; do
+for u in grm_engine grm_lone grm_split grm_probe grm_emit grm_tables grm_cellsums grm_rebin; do
   [ -f "$S/$u.hip" ] || continue
   case $u in
     grm_engine) fl="$FL $SF $VFLAGS";;
